@@ -4,14 +4,24 @@
 One step = one pass of the receive-path classifier (parse + RX checksum
 verdict + PMR -> CoS walk, odpg_classify) over one batch of 2^20 synthetic
 frames already resident in HBM, writing the 4-byte verdict per packet (CoS
-index + RX checksum status, the per-packet outputs the north star names). A
-second timed loop repeats the launches with the loopback_recv pktio counters
-(and the per-CoS / per-queue delivery counts) added in every launch, into the
-sharded device counters odp_pktio_stats reads; it is reported as
-`with_pktio_counters`.
+index + RX checksum status, the per-packet outputs the north star names).
+Under --full a second timed loop repeats the launches with the loopback_recv
+pktio counters (and the per-CoS / per-queue delivery counts) added in every
+launch, into the sharded device counters odp_pktio_stats reads; it is
+reported as `with_pktio_counters`.
 
 Launch:  python bench.py [--gpus N --steps K --warmup W --config c2]
+         python bench.py --full ...       (what the headline does not need)
          torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU)
+A plain run does what the headline needs and no more: set-up, W warmup
+launches, one timed loop of exactly K launches, the line. --full adds the
+second timed loop (`with_pktio_counters`, with its packet-accounting check),
+the CPU baseline, the other configs, and times --runs 5 loops of K launches
+(the line reports the median loop); --no-stats, --no-cpu, --others and --runs
+trim it. --dump-outputs DIR writes what the last launch of the headline loop
+produced (the verdict / port words, and for c5 / tx the frames rewritten in
+place) as DIR/<name>.npy, float64; inputs are seeded, so two builds run with
+the same arguments can be compared output for output.
 `python bench.py --gpus N` with N > 1 and no launcher environment starts the
 N rank processes itself (a torch.distributed.run child process, before any
 GPU call) and exits with its status; under a launcher WORLD_SIZE must equal
@@ -26,11 +36,12 @@ gloo run on one GPU exercises the whole multi-rank path. --source gpu0 adds
 a second workload: each step's batch originates on rank 0's GPU, is
 scattered over the ranks and the verdicts gathered back.
 
-Rank 0 prints one JSON line (contract in the task description) with a
-`roofline` object (kernel time from HIP events on the classify stream) and a
+Rank 0 prints one JSON line with a `roofline` object (kernel time from HIP
+events on the classify stream, the timed loop's own) and, under --full, a
 `cpu_baseline` object (the CPU restatement timed on this host's cores). The
-default 1-GPU run also measures the other BASELINE configs (C1, C2x, C3, C4,
-C5) in the same process and summarises them in `other_configs` (--others).
+default 1-GPU --full run also measures the other BASELINE configs (C1, C2x,
+C3, C4, C5) in the same process and summarises them in `other_configs`
+(--others).
 """
 from __future__ import annotations
 
@@ -53,7 +64,7 @@ METRIC = "Mpps classified (device-resident), 64B pkts × 64 PMR rules"
 
 
 # BASELINE.json's other configs (C1, C3, C4 on one GPU, C5) and SURVEY §8(d)'s
-# second C2 rule mix, measured beside the headline by the default run
+# second C2 rule mix, measured beside the headline by the default --full run
 OTHER_CONFIGS = ("c1", "c2x", "c3", "c4", "c5")
 
 
@@ -62,9 +73,17 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--runs", type=int, default=5,
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the launches with "
+                         "pktio counters, the CPU baseline, the other configs, and the "
+                         "median of 5 timed loops")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the headline loop's last launch produced as "
+                         "DIR/<name>.npy (float64; rank 0's shard)")
+    ap.add_argument("--runs", type=int, default=None,
                     help="timed loops of exactly --steps launches each (after one warmup); "
-                         "the line reports the median run (SURVEY.md 8(d))")
+                         "the line reports the median run (SURVEY.md 8(d)). Default 1, "
+                         "with --full 5")
     ap.add_argument("--config", default="c2", choices=["c1", "c2", "c2x", "c3", "c4", "c5", "tx"])
     ap.add_argument("--fwd-mode", default="hash", choices=["hash", "lpm"],
                     help="c5 only: l3fwd lookup mode")
@@ -74,9 +93,9 @@ def parse_args(argv=None):
                          "Infinity Cache so every launch streams from HBM)")
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
     ap.add_argument("--cpu-threads", type=int, default=0)
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-stats", action="store_true",
-                    help="skip the second timed loop (launches with pktio counters)")
+                    help="--full without the second timed loop (launches with pktio counters)")
     ap.add_argument("--kernel-mode", type=int, default=0,
                     help="0 auto, 1 wave-cooperative walk, 2 evaluate-all, 3 hash walk")
     ap.add_argument("--diag", default="full",
@@ -97,10 +116,16 @@ def parse_args(argv=None):
     ap.add_argument("--others", default=None,
                     help="comma list of further configs measured in the same process and "
                          "summarised in the line's `other_configs` (default on a 1-GPU "
-                         "headline run: " + ",".join(OTHER_CONFIGS) + "; 'none' to skip)")
+                         "headline --full run: " + ",".join(OTHER_CONFIGS) + "; 'none' to skip)")
     ap.add_argument("--others-cpu-seconds", type=float, default=6.0,
                     help="CPU-baseline seconds per further config")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.runs is None:
+        args.runs = 5 if args.full else 1
+    if not args.full:
+        args.no_cpu = args.no_stats = True
+        args.others = "none"
+    return args
 
 
 def _free_port():
@@ -188,6 +213,7 @@ def measure_others(args, cfgs, world, rank, local, dist):
     for c in cfgs:
         a = copy.copy(args)
         a.config, a.others, a.e2e, a.source = c, "none", False, "sharded"
+        a.dump_outputs = None           # the dump is the headline's
         # 100 warmup launches: the first ~10 ms of heavy traffic run with
         # the memory side still clocking up (DESIGN §3 "C3 under the trace")
         a.steps, a.warmup, a.runs = min(args.steps, 100), 100, 3
@@ -325,6 +351,8 @@ def bench_classify(args, world, rank, local, dist):
         return timed_runs(args, ctx, lambda i: launch(i, res), barrier, dist, dev)
 
     wall, kernel_ms, enq_ms, run_ms = timed(results)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args, {"verdict": obufs[(args.steps - 1) % nbuf].download(np.uint32, n)})
     counted = None
     if not args.no_stats:
         wall_st, kernel_ms_st, _, run_ms_st = timed(results_st)
@@ -444,6 +472,24 @@ def timed_runs(args, ctx, launch, barrier, dist, dev):
     order = sorted(range(len(runs)), key=lambda k: runs[k][0])
     med = runs[order[len(runs) // 2]]
     return med[0], med[1], med[2], [round(r[0] * 1e3 / max(args.steps, 1), 5) for r in runs]
+
+
+DUMP_MAX_ELEMS = 2 << 20      # per array, as float64: two arrays stay under 64 MB
+
+
+def dump_outputs(args, arrays):
+    """--dump-outputs: each array of the last timed launch as <name>.npy in
+    float64 (exact for the 32-bit words and the bytes written here). An array
+    of more than DUMP_MAX_ELEMS elements is written as a fixed, seeded sample
+    of its elements (the same indices in every run, in ascending order)."""
+    import numpy as np
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a).reshape(-1)
+        if a.size > DUMP_MAX_ELEMS:
+            idx = np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMS, replace=False)
+            a = a[np.sort(idx)]
+        np.save(os.path.join(args.dump_outputs, name + ".npy"), a.astype(np.float64))
 
 
 def bench_scatter_gather(args, ctx, tbl, frames, n, stride, opt, world, rank, local, dist):
@@ -578,6 +624,9 @@ def bench_tx(args, world, rank, local, dist):
             dist.barrier()
     wall, kernel_ms, enq_ms, run_ms = timed_runs(args, ctx, launch, barrier, dist, dev)
     out = obufs[(args.steps - 1) % nbuf].download(np.uint32, n)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args, {"out": out,
+                            "frames": fbufs[(args.steps - 1) % nbuf].download(np.uint8, 64 * n)})
     assert np.all(out & L.TX_OUT_IPV4) and np.all(out & L.TX_OUT_UDP)
     value = n * world * args.steps / wall / 1e6
     bytes_per_pkt = 64 + 4 + 4           # frame read + two checksum fields + out word
@@ -659,6 +708,9 @@ def bench_l3fwd(args, world, rank, local, dist):
             dist.barrier()
     wall, kernel_ms, enq_ms, run_ms = timed_runs(args, ctx, launch, barrier, dist, dev)
     out = obufs[(args.steps - 1) % nbuf].download(np.int32, n)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args, {"port": out,
+                            "frames": fbufs[(args.steps - 1) % nbuf].download(np.uint8, 64 * n)})
     assert (out >= 0).all(), "every C5 packet is IPv4 and forwarded"
     value = n * world * args.steps / wall / 1e6
     bytes_per_pkt = 64 + 32 + 4          # frame read + header rewrite + port

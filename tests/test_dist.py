@@ -104,7 +104,7 @@ def test_bench_two_ranks_one_gpu(tmp_path):
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(os.path.dirname(HERE), "bench.py"), "--gpus", "2", "--steps", "20",
            "--warmup", "4", "--batch", str(1 << 16), "--no-cpu", "--backend", "gloo",
-           "--source", "gpu0", "--others", "none"]
+           "--source", "gpu0", "--full", "--others", "none"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [x for x in r.stdout.splitlines() if x.startswith("{")]
@@ -152,7 +152,7 @@ def test_bench_rccl_path_on_one_gpu():
     8-GPU run's code path, one rank)."""
     cmd = [sys.executable, os.path.join(os.path.dirname(HERE), "bench.py"), "--gpus", "1",
            "--steps", "20", "--warmup", "4", "--batch", str(1 << 16), "--no-cpu",
-           "--backend", "nccl", "--source", "gpu0", "--others", "none"]
+           "--backend", "nccl", "--source", "gpu0", "--full", "--others", "none"]
     env = dict(os.environ, OMP_NUM_THREADS="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -166,12 +166,12 @@ def test_bench_rccl_path_on_one_gpu():
 
 @pytest.mark.gpu
 def test_bench_other_configs():
-    """The default 1-GPU run's `other_configs`: further configs measured in
+    """The default 1-GPU --full run's `other_configs`: further configs measured in
     the same process, one compact entry each (value, kernel time, roofline
     fraction, traffic ratio, counted-launch time, CPU baseline)."""
     cmd = [sys.executable, os.path.join(os.path.dirname(HERE), "bench.py"), "--steps", "20",
            "--warmup", "4", "--runs", "1", "--batch", str(1 << 16), "--cpu-seconds", "1",
-           "--others", "c1,c3,c5", "--others-cpu-seconds", "1"]
+           "--full", "--others", "c1,c3,c5", "--others-cpu-seconds", "1"]
     r = subprocess.run(cmd, env=dict(os.environ, OMP_NUM_THREADS="2"), capture_output=True,
                        text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -241,7 +241,7 @@ def test_bench_two_ranks_one_gpu_c4_c5(tmp_path, config):
     env = dict(os.environ, OMP_NUM_THREADS="1")
     cmd = [sys.executable, os.path.join(os.path.dirname(HERE), "bench.py"), "--gpus", "2",
            "--config", config, "--steps", "10", "--warmup", "2", "--runs", "2",
-           "--batch", str(1 << 16), "--no-cpu", "--backend", "gloo"]
+           "--batch", str(1 << 16), "--full", "--no-cpu", "--backend", "gloo"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [x for x in r.stdout.splitlines() if x.startswith("{")]

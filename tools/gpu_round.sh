@@ -27,16 +27,16 @@ for s in $STEPS; do
     timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1
     rc=$?; echo "smoke: $rc" | tee -a $OUT/status.txt; tail -3 $OUT/smoke.log; gate $rc ;;
   bench)
-    timeout -k 10 600 python bench.py $BENCH_ARGS > $OUT/bench$T.json 2> $OUT/bench$T.err
+    timeout -k 10 600 python bench.py --full $BENCH_ARGS > $OUT/bench$T.json 2> $OUT/bench$T.err
     rc=$?; echo "bench: $rc" | tee -a $OUT/status.txt; cat $OUT/bench$T.json; tail -3 $OUT/bench$T.err; gate $rc ;;
   prof)
     timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof$T -o run \
-      -- python3 bench.py --no-cpu --steps 100 --warmup 10 $BENCH_ARGS > $OUT/prof$T.log 2>&1
+      -- python3 bench.py --full --no-cpu --steps 100 --warmup 10 $BENCH_ARGS > $OUT/prof$T.log 2>&1
     rc=$?; echo "rocprof stats: $rc" | tee -a $OUT/status.txt; tail -3 $OUT/prof$T.log; gate $rc ;;
   pmc)
     for c in FETCH_SIZE WRITE_SIZE; do
       timeout -k 10 600 rocprofv3 --pmc $c --output-format csv -d $OUT/pmc${T}_$c -o run \
-        -- python3 bench.py --no-cpu --steps 20 --warmup 2 $BENCH_ARGS > $OUT/pmc${T}_$c.log 2>&1
+        -- python3 bench.py --full --no-cpu --steps 20 --warmup 2 $BENCH_ARGS > $OUT/pmc${T}_$c.log 2>&1
       rc=$?; echo "rocprof pmc $c: $rc" | tee -a $OUT/status.txt; tail -2 $OUT/pmc${T}_$c.log; gate $rc
     done ;;
   esac

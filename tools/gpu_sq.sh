@@ -13,12 +13,12 @@ for CFG in ${CFGS:-c2x}; do
   for g in $GROUPS_; do
     i=$((i+1))
     timeout -k 10 240 rocprofv3 --pmc ${g//,/ } --output-format csv -d $OUT/p$i -o run \
-      -- python3 bench.py --no-cpu --no-stats --config $CFG --steps 20 --warmup 2 ${BENCH_ARGS:-} > $OUT/p$i.log 2>&1
+      -- python3 bench.py --full --no-cpu --no-stats --config $CFG --steps 20 --warmup 2 ${BENCH_ARGS:-} > $OUT/p$i.log 2>&1
     rc=$?; echo "pmc $CFG $g: $rc" | tee -a $OUT/status.txt
     if [ $rc -ne 0 ]; then tail -5 $OUT/p$i.log; exit $rc; fi
   done
   python tools/pmc_summary.py $OUT > $OUT/summary.json 2>&1
-  timeout -k 10 300 python bench.py --no-cpu --config $CFG > $OUT/bench.json 2> $OUT/bench.err
+  timeout -k 10 300 python bench.py --full --no-cpu --config $CFG > $OUT/bench.json 2> $OUT/bench.err
   rc=$?; echo "bench $CFG: $rc"; cat $OUT/bench.json
   [ $rc -eq 0 ] || exit $rc
 done

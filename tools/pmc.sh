@@ -13,7 +13,7 @@ i=0
 for g in $GROUPS_; do
   i=$((i+1))
   timeout -k 10 300 rocprofv3 --pmc ${g//,/ } --output-format csv -d $OUT/p$i -o run \
-    -- python3 bench.py --no-cpu --config $CFG --steps 20 --warmup 2 ${BENCH_ARGS:-} > $OUT/p$i.log 2>&1
+    -- python3 bench.py --full --no-cpu --config $CFG --steps 20 --warmup 2 ${BENCH_ARGS:-} > $OUT/p$i.log 2>&1
   rc=$?; echo "pmc $g: $rc" | tee -a $OUT/status.txt
   if [ $rc -ne 0 ]; then tail -5 $OUT/p$i.log; exit $rc; fi
 done
