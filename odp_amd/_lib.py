@@ -151,6 +151,18 @@ class odpg_tx_cfg_t(C.Structure):
 TX_META_FIELDS = [("l3_offset", "<u2"), ("l4_offset", "<u2"), ("flags", "<u4")]   # 8 B
 
 
+# ---- include/odpg_deliver.h -------------------------------------------------
+DELIVER_TILE = 4096      # ODPG_DELIVER_TILE: packets one workgroup ranks
+
+
+def deliver_pktin(nbuckets):
+    return nbuckets - 2
+
+
+def deliver_free(nbuckets):
+    return nbuckets - 1
+
+
 # ---- include/odpg_pcap.h ----------------------------------------------------
 class odpg_capture_t(C.Structure):
     _fields_ = [("frames", C.c_void_p), ("desc", C.c_void_p), ("num", C.c_uint32),
@@ -386,6 +398,13 @@ SIGNATURES = {
     "odpg_pcap_free": (None, [C.POINTER(odpg_capture_t)]),
     # include/odpg_tx.h
     "odpg_tx_prepare": (_i32, [_vp, C.POINTER(odpg_tx_batch_t), C.POINTER(odpg_tx_cfg_t), _vp]),
+    # include/odpg_deliver.h
+    "odpg_deliver_create": (_i32, [_vp, _vp, _u32, C.POINTER(_vp)]),
+    "odpg_deliver_destroy": (None, [_vp]),
+    "odpg_deliver_num_buckets": (_u32, [_vp]),
+    "odpg_deliver_queue_base": (_i32, [_vp, _u32]),
+    "odpg_deliver_match": (_i32, [_vp, _vp]),
+    "odpg_deliver": (_i32, [_vp, _vp, _u32, _vp, _vp]),
     # include/odpg_group.h
     "odpg_group_create": (_i32, [C.POINTER(C.c_int), _u32, C.POINTER(_vp)]),
     "odpg_group_destroy": (None, [_vp]),

@@ -9,6 +9,7 @@
 #include <stdio.h>
 #include <string.h>
 #include <stdlib.h>
+#include <algorithm>
 #include <atomic>
 #include <mutex>
 #include <new>
@@ -18,6 +19,7 @@
 #include "odpg_internal.h"
 #include "stats_commit.h"
 #include "cls_compile.h"
+#include "deliver.h"
 
 
 extern "C" int odpg_launch_classify(const odpg_launch_args *a, hipStream_t s);
@@ -482,6 +484,26 @@ int odpg_table_has_cycle(const odpg_table_t *t)
 extern "C" int odpg_launch_counters_fold(uint64_t *rows, uint32_t nrows, uint32_t words,
 					 uint64_t *sum, hipStream_t s);
 
+/* queue columns of a table: CoS c has nq[c] = max(num_queue, 1) queues, the
+ * first in column qcol[c]; qcol[num_cos] = the columns in all (the layout of
+ * the sharded counters' delivery block and of the delivery lists' buckets) */
+static void table_queue_cols(const odpg_table_t *t, std::vector<uint32_t> &qcol,
+			     std::vector<uint8_t> &nq)
+{
+	const dcos_t *hc = (const dcos_t *)(t->blob.data() + t->hdr.cos_off);
+	const uint32_t n = t->hdr.num_cos;
+	uint32_t col = 0;
+
+	qcol.resize(n + 1u);
+	nq.resize(n);
+	for (uint32_t i = 0; i < n; i++) {
+		qcol[i] = col;
+		nq[i] = (uint8_t)(hc[i].num_queue ? hc[i].num_queue : 1u);
+		col += nq[i];
+	}
+	qcol[n] = col;
+}
+
 static void counters_free(odpg_counters_t *k)
 {
 	odpg_ctx_t *c = k->ctx;
@@ -511,18 +533,10 @@ int odpg_counters_create(odpg_ctx_t *c, const odpg_table_t *t, odpg_counters_t *
 	odpg_ctx_ref(c);
 	k->qsig = t->qsig;
 	k->ncos = h.num_cos;
-	k->qcol.resize(h.num_cos + 1u);
-	k->nq.resize(h.num_cos);
-	uint32_t col = 0;
-
-	for (uint32_t i = 0; i < h.num_cos; i++) {
-		k->qcol[i] = col;
-		k->nq[i] = (uint8_t)(hc[i].num_queue ? hc[i].num_queue : 1u);
-		col += k->nq[i];
+	table_queue_cols(t, k->qcol, k->nq);
+	for (uint32_t i = 0; i < h.num_cos; i++)
 		k->any_cos |= hc[i].stats ? 1u : 0u;
-	}
-	k->qcol[h.num_cos] = col;
-	k->ncols = col;
+	k->ncols = k->qcol[h.num_cos];
 	k->words = 4u + k->ncos + k->ncols;
 	if (((size_t)k->ncos + k->ncols) * 4u > CNT_MAX_LDS) {
 		counters_free(k);
@@ -614,6 +628,134 @@ int odpg_counters_fold(odpg_counters_t *k, uint64_t *words)
 		for (uint32_t q = 0; q < k->nq[i]; q++)
 			uq[(size_t)i * ODPG_COS_QUEUE_MAX + q] += dl[k->qcol[i] + q];
 	return 0;
+}
+
+/* ---- delivery lists (odpg_deliver.h; kernels in deliver.hip) ------------- */
+struct odpg_deliver_s {
+	odpg_ctx_t *ctx;
+	uint32_t max_pkts;
+	std::vector<uint32_t> qcol;    /* host: qbase, ncos + 1 */
+	std::vector<uint8_t> nq;
+	odpg_deliver_args a;           /* layout + device workspace */
+};
+
+static void deliver_free(odpg_deliver_t *d)
+{
+	odpg_ctx_t *c = d->ctx;
+
+	hipFree((void *)d->a.qbase);
+	hipFree(d->a.hist);
+	hipFree(d->a.dtotal);
+	hipFree(d->a.bcount);
+	hipFree(d->a.pairs);
+	delete d;
+	odpg_ctx_unref(c);
+}
+
+int odpg_deliver_create(odpg_ctx_t *c, const odpg_table_t *t, uint32_t max_pkts,
+			odpg_deliver_t **out)
+{
+	/* packet positions and tile starts are 32-bit sums below 2^32 */
+	if (!c || !t || !out || max_pkts > (1u << 31))
+		return -EINVAL;
+	if (t->device != c->device)
+		return -EXDEV;
+	odpg_deliver_t *d = new odpg_deliver_t();
+	odpg_deliver_args &a = d->a;
+
+	d->ctx = c;
+	odpg_ctx_ref(c);
+	d->max_pkts = max_pkts;
+	table_queue_cols(t, d->qcol, d->nq);
+	a.num_cos = t->hdr.num_cos;
+	a.nbuckets = d->qcol[a.num_cos] + 2u;
+	a.key_bits = dlv_key_bits(a.nbuckets);
+	const bool two = a.key_bits > DLV_DIGIT_BITS;
+	const size_t tiles = ((size_t)max_pkts + DLV_TILE - 1u) / DLV_TILE;
+	const size_t hist_words = std::max<size_t>(tiles, 1u) << dlv_bits0(a.key_bits);
+	const size_t qb = (size_t)(a.num_cos + 1u) * 4u;
+	hipEvent_t ready = nullptr;
+	int rc = -ENOMEM;
+
+	hipSetDevice(c->device);
+	if (hipMalloc((void **)&a.qbase, qb) == hipSuccess &&
+	    hipMalloc(&a.hist, hist_words * 4u) == hipSuccess &&
+	    hipMalloc(&a.dtotal, DLV_RADIX * 4u) == hipSuccess &&
+	    (!two || (hipMalloc(&a.bcount, (size_t)a.nbuckets * 4u) == hipSuccess &&
+		      hipMalloc(&a.pairs, std::max<size_t>(max_pkts, 1u) * 8u) == hipSuccess)) &&
+	    hipEventCreateWithFlags(&ready, hipEventDisableTiming) == hipSuccess) {
+		std::lock_guard<std::mutex> g(c->lock);
+
+		rc = -EIO;
+		if (hipMemcpyAsync((void *)a.qbase, d->qcol.data(), qb, hipMemcpyHostToDevice,
+				   c->stream) == hipSuccess &&
+		    odpg_launch_deliver_clear(a.dtotal, DLV_RADIX, c->stream) == 0 &&
+		    (!two || odpg_launch_deliver_clear(a.bcount, a.nbuckets, c->stream) == 0) &&
+		    hipEventRecord(ready, c->stream) == hipSuccess)
+			rc = 0;
+	}
+	/* the upload reads d->qcol: done before the plan is handed out */
+	if (rc == 0 && hipEventSynchronize(ready) != hipSuccess)
+		rc = -EIO;
+	if (ready)
+		hipEventDestroy(ready);
+	if (rc) {
+		deliver_free(d);
+		return rc;
+	}
+	*out = d;
+	return 0;
+}
+
+void odpg_deliver_destroy(odpg_deliver_t *d)
+{
+	if (!d)
+		return;
+	hipSetDevice(d->ctx->device);
+	hipStreamSynchronize(d->ctx->stream);   /* launches still using the workspace */
+	deliver_free(d);
+}
+
+uint32_t odpg_deliver_num_buckets(const odpg_deliver_t *d)
+{
+	return d ? d->a.nbuckets : 0u;
+}
+
+int odpg_deliver_queue_base(const odpg_deliver_t *d, uint32_t cos)
+{
+	if (!d || cos >= d->a.num_cos)
+		return -EINVAL;
+	return (int)d->qcol[cos];
+}
+
+int odpg_deliver_match(const odpg_deliver_t *d, const odpg_table_t *t)
+{
+	if (!d || !t || d->a.num_cos != t->hdr.num_cos)
+		return 0;
+	const dcos_t *hc = (const dcos_t *)(t->blob.data() + t->hdr.cos_off);
+
+	for (uint32_t i = 0; i < d->a.num_cos; i++)
+		if (d->nq[i] != (hc[i].num_queue ? hc[i].num_queue : 1u))
+			return 0;
+	return 1;
+}
+
+int odpg_deliver(odpg_deliver_t *d, const odpg_out_t *out, uint32_t num, uint32_t *order,
+		 uint32_t *offsets)
+{
+	if (!d || !out || !order || !offsets || num > d->max_pkts)
+		return -EINVAL;
+	odpg_ctx_t *c = d->ctx;
+	odpg_deliver_args a = d->a;
+
+	a.out = out;
+	a.num = num;
+	a.order = order;
+	a.offsets = offsets;
+	hipSetDevice(c->device);
+	std::lock_guard<std::mutex> g(c->lock);
+
+	return odpg_launch_deliver(&a, c->stream);
 }
 
 static int ensure_ws(odpg_ctx_t *c, size_t bytes)

@@ -128,6 +128,63 @@ class Counters:
             pass
 
 
+class Deliver:
+    """Delivery-list plan of one table layout (include/odpg_deliver.h): from
+    verdict words, per destination queue the packet indices in arrival
+    order, on the device."""
+
+    def __init__(self, ctx, table, max_pkts):
+        h = C.c_void_p()
+        L.check(lib.odpg_deliver_create(ctx.h, table.h, max_pkts, C.byref(h)),
+                "odpg_deliver_create")
+        self.h = h.value
+        self.ctx = ctx
+        self.max_pkts = max_pkts
+        self.num_cos = table.num_cos
+        self.num_buckets = lib.odpg_deliver_num_buckets(self.h)
+
+    def queue_base(self, cos):
+        """First bucket of CoS `cos` (bucket = queue_base + hash queue)."""
+        b = lib.odpg_deliver_queue_base(self.h, cos)
+        if b < 0:
+            raise L.OdpgError(f"odpg_deliver_queue_base({cos}) failed: {b}")
+        return b
+
+    def run_dev(self, out_buf, num, order_buf, offsets_buf):
+        """Asynchronous on the context stream: order_buf gets num indices,
+        offsets_buf num_buckets + 1 words."""
+        L.check(lib.odpg_deliver(self.h, out_buf.ptr, num, order_buf.ptr, offsets_buf.ptr),
+                "odpg_deliver")
+
+    def run(self, out_words):
+        """Upload verdict words, build the lists, download (order, offsets)."""
+        w = np.ascontiguousarray(out_words, dtype=np.uint32)
+        ob = self.ctx.buffer(w.nbytes)
+        ob.upload(w)
+        rb = self.ctx.buffer(w.nbytes)
+        fb = self.ctx.buffer(4 * (self.num_buckets + 1))
+        self.run_dev(ob, len(w), rb, fb)
+        self.ctx.sync()
+        res = rb.download(np.uint32, len(w)), fb.download(np.uint32, self.num_buckets + 1)
+        for b in (ob, rb, fb):
+            b.free()
+        return res
+
+    def close(self):
+        if self.h:
+            # valid after the context's destroy too (odpg.h "object lifetimes")
+            lib.odpg_deliver_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        if sys.is_finalizing():   # the HIP runtime may be torn down already
+            return
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Context:
     def __init__(self, device=0, stream=None):
         n = lib.odpg_device_count()
@@ -166,6 +223,9 @@ class Context:
 
     def counters(self, table):
         return Counters(self, table)
+
+    def deliver(self, table, max_pkts=1 << 20):
+        return Deliver(self, table, max_pkts)
 
     def classify_dev(self, table, frames_buf, num, stride=0, desc_buf=None, opt=0,
                      layer=L.LAYER_ALL, classify=True, out_buf=None, mark_buf=None,
