@@ -163,6 +163,27 @@ def deliver_free(nbuckets):
     return nbuckets - 1
 
 
+# ---- include/odpg_gather.h --------------------------------------------------
+GATHER_TILE = 1024       # ODPG_GATHER_TILE: positions one workgroup handles
+
+
+class odpg_gather_src_t(C.Structure):
+    _fields_ = [("frames", C.c_void_p), ("desc", C.c_void_p), ("stride", C.c_uint32),
+                ("num", C.c_uint32), ("words", C.c_void_p)]
+
+
+class odpg_gather_total_t(C.Structure):
+    _fields_ = [("num", C.c_uint32), ("copied", C.c_uint32), ("bytes", C.c_uint64)]
+
+
+class odpg_gather_dst_t(C.Structure):
+    _fields_ = [("frames", C.c_void_p), ("capacity", C.c_uint64), ("desc", C.c_void_p),
+                ("words", C.c_void_p), ("total", C.c_void_p)]
+
+
+GATHER_TOTAL_FIELDS = [("num", "<u4"), ("copied", "<u4"), ("bytes", "<u8")]   # 16 B
+
+
 # ---- include/odpg_pcap.h ----------------------------------------------------
 class odpg_capture_t(C.Structure):
     _fields_ = [("frames", C.c_void_p), ("desc", C.c_void_p), ("num", C.c_uint32),
@@ -405,6 +426,11 @@ SIGNATURES = {
     "odpg_deliver_queue_base": (_i32, [_vp, _u32]),
     "odpg_deliver_match": (_i32, [_vp, _vp]),
     "odpg_deliver": (_i32, [_vp, _vp, _u32, _vp, _vp]),
+    # include/odpg_gather.h
+    "odpg_gather_create": (_i32, [_vp, _u32, C.POINTER(_vp)]),
+    "odpg_gather_destroy": (None, [_vp]),
+    "odpg_gather": (_i32, [_vp, C.POINTER(odpg_gather_src_t), _vp, _vp, _u32, _u32,
+                           C.POINTER(odpg_gather_dst_t)]),
     # include/odpg_group.h
     "odpg_group_create": (_i32, [C.POINTER(C.c_int), _u32, C.POINTER(_vp)]),
     "odpg_group_destroy": (None, [_vp]),

@@ -20,6 +20,7 @@
 #include "stats_commit.h"
 #include "cls_compile.h"
 #include "deliver.h"
+#include "gather.h"
 
 
 extern "C" int odpg_launch_classify(const odpg_launch_args *a, hipStream_t s);
@@ -756,6 +757,73 @@ int odpg_deliver(odpg_deliver_t *d, const odpg_out_t *out, uint32_t num, uint32_
 	std::lock_guard<std::mutex> g(c->lock);
 
 	return odpg_launch_deliver(&a, c->stream);
+}
+
+/* ---- dense queue batches (odpg_gather.h; kernels in gather.hip) ----------- */
+struct odpg_gather_s {
+	odpg_ctx_t *ctx;
+	uint32_t max_pkts;
+	uint64_t *tsum;                /* device: a word per tile */
+	odpg_desc_t *pos;              /* device: max_pkts source descriptors */
+};
+
+static void gather_free(odpg_gather_t *g)
+{
+	odpg_ctx_t *c = g->ctx;
+
+	hipFree(g->tsum);
+	hipFree(g->pos);
+	delete g;
+	odpg_ctx_unref(c);
+}
+
+int odpg_gather_create(odpg_ctx_t *c, uint32_t max_pkts, odpg_gather_t **out)
+{
+	/* positions are 32-bit sums below 2^32, as in a delivery plan */
+	if (!c || !out || max_pkts > (1u << 31))
+		return -EINVAL;
+	odpg_gather_t *g = new odpg_gather_t();
+	const size_t tiles = ((size_t)max_pkts + GTH_TILE - 1u) / GTH_TILE;
+
+	g->ctx = c;
+	odpg_ctx_ref(c);
+	g->max_pkts = max_pkts;
+	hipSetDevice(c->device);
+	if (hipMalloc(&g->tsum, std::max<size_t>(tiles, 1u) * 8u) != hipSuccess ||
+	    hipMalloc(&g->pos, std::max<size_t>(max_pkts, 1u) * sizeof(odpg_desc_t)) != hipSuccess) {
+		gather_free(g);
+		return -ENOMEM;
+	}
+	*out = g;
+	return 0;
+}
+
+void odpg_gather_destroy(odpg_gather_t *g)
+{
+	if (!g)
+		return;
+	hipSetDevice(g->ctx->device);
+	hipStreamSynchronize(g->ctx->stream);   /* launches still using the workspace */
+	gather_free(g);
+}
+
+int odpg_gather(odpg_gather_t *g, const odpg_gather_src_t *src, const uint32_t *order,
+		const uint32_t *offsets, uint32_t b_first, uint32_t b_last,
+		const odpg_gather_dst_t *dst)
+{
+	if (!g || !src || !order || !offsets || !dst || !dst->frames || !dst->total ||
+	    (!src->frames && src->num) || (((uintptr_t)src->frames | (uintptr_t)dst->frames) & 15u) ||
+	    src->num > g->max_pkts || b_first > b_last || dst->capacity > (1ull << 32) ||
+	    (!src->desc && (!src->stride || (src->stride & 15u))) || (src->desc && !dst->desc) ||
+	    !src->words != !dst->words)
+		return -EINVAL;
+	odpg_ctx_t *c = g->ctx;
+	odpg_gather_args a = {*src, *dst, order, offsets, b_first, b_last, g->tsum, g->pos};
+
+	hipSetDevice(c->device);
+	std::lock_guard<std::mutex> lk(c->lock);
+
+	return odpg_launch_gather(&a, c->stream);
 }
 
 static int ensure_ws(odpg_ctx_t *c, size_t bytes)

@@ -185,6 +185,86 @@ class Deliver:
             pass
 
 
+class Gather:
+    """Gather plan (include/odpg_gather.h): the frames of a range of delivery
+    buckets written back to back in delivery order, on the device."""
+
+    def __init__(self, ctx, max_pkts):
+        h = C.c_void_p()
+        L.check(lib.odpg_gather_create(ctx.h, max_pkts, C.byref(h)), "odpg_gather_create")
+        self.h = h.value
+        self.ctx = ctx
+        self.max_pkts = max_pkts
+
+    def run_dev(self, frames_buf, num, order_buf, offsets_buf, b_first, b_last, dst_buf,
+                capacity, total_buf, stride=0, desc_buf=None, words_buf=None,
+                dst_desc_buf=None, dst_words_buf=None):
+        """Asynchronous on the context stream: buckets [b_first, b_last) of
+        the lists into dst_buf (capacity bytes), dst_desc_buf / dst_words_buf
+        (num entries) and total_buf (odpg_gather_total_t)."""
+        s = L.odpg_gather_src_t(frames_buf.ptr, desc_buf.ptr if desc_buf else None, stride, num,
+                                words_buf.ptr if words_buf else None)
+        d = L.odpg_gather_dst_t(dst_buf.ptr, capacity,
+                                dst_desc_buf.ptr if dst_desc_buf else None,
+                                dst_words_buf.ptr if dst_words_buf else None, total_buf.ptr)
+        L.check(lib.odpg_gather(self.h, C.byref(s), order_buf.ptr, offsets_buf.ptr, b_first,
+                                b_last, C.byref(d)), "odpg_gather")
+
+    def run(self, frames, order, offsets, b_first, b_last, stride=0, desc=None, words=None,
+            capacity=None, fill=0):
+        """Upload, gather, download (frames, desc, words, total). The source
+        batch has len(order) frames. Every destination buffer is set to the
+        byte `fill` first; frames come back as capacity + 64 bytes (the slack
+        frame buffers carry), desc and words with one entry per source frame,
+        total as a GATHER_TOTAL_FIELDS record. capacity defaults to the room
+        every source frame would need."""
+        _, desc_dt = L.np_dtypes()
+        num = len(order)
+        if desc is not None:
+            desc = np.ascontiguousarray(desc, dtype=desc_dt)
+            room = int(((desc["len"].astype(np.int64) + 15) // 16 * 16).sum())
+        else:
+            room = num * stride
+        cap = room if capacity is None else int(capacity)
+        src = [np.ascontiguousarray(frames, dtype=np.uint8),
+               np.ascontiguousarray(order, dtype=np.uint32),
+               np.ascontiguousarray(offsets, dtype=np.uint32), desc,
+               None if words is None else np.ascontiguousarray(words, dtype=np.uint32)]
+        fb, rb, sb, db, wb = (None if a is None else self.ctx.buffer(a.nbytes + 64) for a in src)
+        for b, a in zip((fb, rb, sb, db, wb), src):
+            if b:
+                b.upload(a)
+        out = [self.ctx.buffer(cap + 64), self.ctx.buffer(8 * num), self.ctx.buffer(16),
+               self.ctx.buffer(4 * num) if wb else None]
+        for b in out:
+            if b:
+                L.check(lib.odpg_memset_dev(self.ctx.h, b.ptr, fill, b.nbytes), "memset")
+        self.run_dev(fb, num, rb, sb, b_first, b_last, out[0], cap, out[2], stride, db, wb,
+                     out[1], out[3])
+        self.ctx.sync()
+        res = (out[0].download(np.uint8, cap + 64), out[1].download(desc_dt, num),
+               out[3].download(np.uint32, num) if wb else None,
+               out[2].download(np.dtype(L.GATHER_TOTAL_FIELDS), 1)[0])
+        for b in (fb, rb, sb, db, wb, *out):
+            if b:
+                b.free()
+        return res
+
+    def close(self):
+        if self.h:
+            # valid after the context's destroy too (odpg.h "object lifetimes")
+            lib.odpg_gather_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        if sys.is_finalizing():   # the HIP runtime may be torn down already
+            return
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Context:
     def __init__(self, device=0, stream=None):
         n = lib.odpg_device_count()
@@ -226,6 +306,9 @@ class Context:
 
     def deliver(self, table, max_pkts=1 << 20):
         return Deliver(self, table, max_pkts)
+
+    def gather(self, max_pkts=1 << 20):
+        return Gather(self, max_pkts)
 
     def classify_dev(self, table, frames_buf, num, stride=0, desc_buf=None, opt=0,
                      layer=L.LAYER_ALL, classify=True, out_buf=None, mark_buf=None,
