@@ -230,12 +230,13 @@ int         odpg_device_count(void);
  * the context create its own non-blocking stream.
  *
  * Object lifetimes: tables, counters, forwarders (odpg_fwd.h), delivery
- * plans (odpg_deliver.h), gather plans (odpg_gather.h) and fences may be
- * destroyed in any order relative to each other and to their context.
+ * plans (odpg_deliver.h), gather plans (odpg_gather.h), segmentation plans
+ * (odpg_lso.h) and fences may be destroyed in any order relative to each
+ * other and to their context.
  * odpg_ctx_destroy() releases the caller's handle and the odp_cls bindings
- * made on the context; counters, forwarders, delivery and gather plans and
- * fences created on it hold a reference, and the context's stream and
- * device memory are freed when the last of them is destroyed (the context
+ * made on the context; counters, forwarders, delivery, gather and
+ * segmentation plans and fences created on it hold a reference, and the
+ * context's stream and device memory are freed when the last of them is destroyed (the context
  * handle itself may not be used after odpg_ctx_destroy). A table refers to
  * its device only. */
 int  odpg_ctx_create(int device, void *stream, odpg_ctx_t **ctx);

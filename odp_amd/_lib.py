@@ -184,6 +184,68 @@ class odpg_gather_dst_t(C.Structure):
 GATHER_TOTAL_FIELDS = [("num", "<u4"), ("copied", "<u4"), ("bytes", "<u8")]   # 16 B
 
 
+# ---- include/odpg_lso.h -----------------------------------------------------
+LSO_TILE = 64            # ODPG_LSO_TILE: packets one copy workgroup handles
+LSO_PROTO_CUSTOM, LSO_PROTO_IPV4 = 1, 2
+LSO_ADD_SEGMENT_NUM, LSO_WRITE_BITS = 1, 5
+LSO_MAX_CUSTOM, LSO_MAX_PROFILES, LSO_MAX_SEGMENTS, LSO_MAX_PAYLOAD_OFFSET = 8, 16, 64, 128
+(LSO_OK, LSO_BAD_PROFILE, LSO_BAD_OFFSET, LSO_BAD_L3, LSO_BAD_PAYLOAD, LSO_TOO_MANY,
+ LSO_BAD_IHL, LSO_BAD_FIELD) = range(8)
+
+
+class odpg_lso_bits_t(C.Structure):
+    _fields_ = [("mask", C.c_uint8), ("value", C.c_uint8)]
+
+
+class odpg_lso_field_t(C.Structure):
+    _fields_ = [("mod_op", C.c_uint8), ("size", C.c_uint8), ("offset", C.c_uint16),
+                ("first", odpg_lso_bits_t), ("middle", odpg_lso_bits_t),
+                ("last", odpg_lso_bits_t), ("reserved", C.c_uint16)]
+
+
+class odpg_lso_profile_t(C.Structure):
+    _fields_ = [("proto", C.c_uint32), ("num_custom", C.c_uint32),
+                ("field", odpg_lso_field_t * LSO_MAX_CUSTOM)]
+
+
+class odpg_lso_opt_t(C.Structure):
+    _fields_ = [("payload_offset", C.c_uint16), ("max_payload_len", C.c_uint16),
+                ("l3_offset", C.c_uint16), ("profile", C.c_uint8), ("reserved", C.c_uint8)]
+
+
+class odpg_lso_src_t(C.Structure):
+    _fields_ = [("frames", C.c_void_p), ("desc", C.c_void_p), ("stride", C.c_uint32),
+                ("num", C.c_uint32), ("opt", C.c_void_p), ("uniform", odpg_lso_opt_t)]
+
+
+class odpg_lso_total_t(C.Structure):
+    _fields_ = [("num_segs", C.c_uint32), ("copied", C.c_uint32), ("first_bad", C.c_uint32),
+                ("reserved", C.c_uint32), ("bytes", C.c_uint64)]
+
+
+class odpg_lso_dst_t(C.Structure):
+    _fields_ = [("frames", C.c_void_p), ("capacity", C.c_uint64), ("desc", C.c_void_p),
+                ("max_segs", C.c_uint32), ("reserved", C.c_uint32), ("seg_first", C.c_void_p),
+                ("status", C.c_void_p), ("total", C.c_void_p)]
+
+
+LSO_OPT_FIELDS = [("payload_offset", "<u2"), ("max_payload_len", "<u2"), ("l3_offset", "<u2"),
+                  ("profile", "u1"), ("reserved", "u1")]                       # 8 B
+LSO_TOTAL_FIELDS = [("num_segs", "<u4"), ("copied", "<u4"), ("first_bad", "<u4"),
+                    ("reserved", "<u4"), ("bytes", "<u8")]                     # 24 B
+
+
+def lso_profile(proto, fields=()):
+    """odpg_lso_profile_t from (mod_op, offset, size[, first, middle, last]) tuples;
+    first / middle / last are (mask, value) pairs of WRITE_BITS."""
+    p = odpg_lso_profile_t(proto=proto, num_custom=len(fields))
+    for f, (op, off, size, *bits) in zip(p.field, fields):
+        f.mod_op, f.offset, f.size = op, off, size
+        for name, (m, v) in zip(("first", "middle", "last"), bits):
+            setattr(f, name, odpg_lso_bits_t(m, v))
+    return p
+
+
 # ---- include/odpg_pcap.h ----------------------------------------------------
 class odpg_capture_t(C.Structure):
     _fields_ = [("frames", C.c_void_p), ("desc", C.c_void_p), ("num", C.c_uint32),
@@ -431,6 +493,11 @@ SIGNATURES = {
     "odpg_gather_destroy": (None, [_vp]),
     "odpg_gather": (_i32, [_vp, C.POINTER(odpg_gather_src_t), _vp, _vp, _u32, _u32,
                            C.POINTER(odpg_gather_dst_t)]),
+    # include/odpg_lso.h
+    "odpg_lso_profile_check": (_i32, [C.POINTER(odpg_lso_profile_t)]),
+    "odpg_lso_create": (_i32, [_vp, C.POINTER(odpg_lso_profile_t), _u32, _u32, C.POINTER(_vp)]),
+    "odpg_lso_destroy": (None, [_vp]),
+    "odpg_lso": (_i32, [_vp, C.POINTER(odpg_lso_src_t), C.POINTER(odpg_lso_dst_t)]),
     # include/odpg_group.h
     "odpg_group_create": (_i32, [C.POINTER(C.c_int), _u32, C.POINTER(_vp)]),
     "odpg_group_destroy": (None, [_vp]),

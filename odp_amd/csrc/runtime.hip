@@ -21,6 +21,7 @@
 #include "cls_compile.h"
 #include "deliver.h"
 #include "gather.h"
+#include "lso.h"
 
 
 extern "C" int odpg_launch_classify(const odpg_launch_args *a, hipStream_t s);
@@ -824,6 +825,111 @@ int odpg_gather(odpg_gather_t *g, const odpg_gather_src_t *src, const uint32_t *
 	std::lock_guard<std::mutex> lk(c->lock);
 
 	return odpg_launch_gather(&a, c->stream);
+}
+
+/* ---- segmentation offload (odpg_lso.h; kernels in lso.hip) ----------------- */
+struct odpg_lso_s {
+	odpg_ctx_t *ctx;
+	uint32_t max_pkts, num_profiles;
+	odpg_lso_profile_t *profiles;  /* device */
+	odpg_lso_pk *pk;               /* device: max_pkts records */
+	uint64_t *tunits;              /* device: a word per tile, each */
+	uint32_t *tsegs, *tbad;
+};
+
+/* odp_lso_profile_create (odp_packet_io.c:2836-2885) */
+int odpg_lso_profile_check(const odpg_lso_profile_t *p)
+{
+	if (!p || (p->proto != ODPG_LSO_PROTO_IPV4 && p->proto != ODPG_LSO_PROTO_CUSTOM))
+		return -EINVAL;
+	if (p->proto != ODPG_LSO_PROTO_CUSTOM)
+		return 0;
+	if (p->num_custom > ODPG_LSO_MAX_CUSTOM)
+		return -EINVAL;
+	for (uint32_t i = 0; i < p->num_custom; i++) {
+		const odpg_lso_field_t &f = p->field[i];
+
+		if (f.offset > ODPG_LSO_MAX_PAYLOAD_OFFSET ||
+		    (f.mod_op != ODPG_LSO_ADD_SEGMENT_NUM && f.mod_op != ODPG_LSO_WRITE_BITS) ||
+		    (f.mod_op == ODPG_LSO_WRITE_BITS && f.size != 1u) ||
+		    (f.size != 1u && f.size != 2u && f.size != 4u && f.size != 8u))
+			return -EINVAL;
+	}
+	return 0;
+}
+
+static void lso_free(odpg_lso_t *l)
+{
+	odpg_ctx_t *c = l->ctx;
+
+	hipFree(l->profiles);
+	hipFree(l->pk);
+	hipFree(l->tunits);
+	hipFree(l->tsegs);
+	hipFree(l->tbad);
+	delete l;
+	odpg_ctx_unref(c);
+}
+
+int odpg_lso_create(odpg_ctx_t *c, const odpg_lso_profile_t *profiles, uint32_t num_profiles,
+		    uint32_t max_pkts, odpg_lso_t **out)
+{
+	/* 64 segments a packet: positions stay below 2^32 */
+	if (!c || !profiles || !out || !num_profiles || num_profiles > ODPG_LSO_MAX_PROFILES ||
+	    max_pkts > (1u << 25))
+		return -EINVAL;
+	for (uint32_t i = 0; i < num_profiles; i++)
+		if (odpg_lso_profile_check(&profiles[i]))
+			return -EINVAL;
+	odpg_lso_t *l = new odpg_lso_t();
+	const size_t tiles = std::max<size_t>(((size_t)max_pkts + LSO_TILE - 1u) / LSO_TILE, 1u);
+	const size_t pb = num_profiles * sizeof(odpg_lso_profile_t);
+	int rc = -ENOMEM;
+
+	l->ctx = c;
+	odpg_ctx_ref(c);
+	l->max_pkts = max_pkts;
+	l->num_profiles = num_profiles;
+	hipSetDevice(c->device);
+	if (hipMalloc(&l->profiles, pb) == hipSuccess &&
+	    hipMalloc(&l->pk, std::max<size_t>(max_pkts, 1u) * sizeof(odpg_lso_pk)) == hipSuccess &&
+	    hipMalloc(&l->tunits, tiles * 8u) == hipSuccess &&
+	    hipMalloc(&l->tsegs, tiles * 4u) == hipSuccess &&
+	    hipMalloc(&l->tbad, tiles * 4u) == hipSuccess)
+		/* synchronous: `profiles` is the caller's again on return */
+		rc = hipMemcpy(l->profiles, profiles, pb, hipMemcpyHostToDevice) == hipSuccess ? 0 : -EIO;
+	if (rc) {
+		lso_free(l);
+		return rc;
+	}
+	*out = l;
+	return 0;
+}
+
+void odpg_lso_destroy(odpg_lso_t *l)
+{
+	if (!l)
+		return;
+	hipSetDevice(l->ctx->device);
+	hipStreamSynchronize(l->ctx->stream);   /* launches still using the workspace */
+	lso_free(l);
+}
+
+int odpg_lso(odpg_lso_t *l, const odpg_lso_src_t *src, const odpg_lso_dst_t *dst)
+{
+	if (!l || !src || !dst || !dst->frames || !dst->seg_first || !dst->status || !dst->total ||
+	    (!dst->desc && dst->max_segs) || (!src->frames && src->num) ||
+	    (((uintptr_t)src->frames | (uintptr_t)dst->frames) & 15u) || src->num > l->max_pkts ||
+	    (!src->desc && (!src->stride || (src->stride & 15u))) || dst->capacity > (1ull << 32))
+		return -EINVAL;
+	odpg_ctx_t *c = l->ctx;
+	odpg_lso_args a = {*src, *dst, l->profiles, l->num_profiles, l->pk, l->tunits, l->tsegs,
+			   l->tbad};
+
+	hipSetDevice(c->device);
+	std::lock_guard<std::mutex> lk(c->lock);
+
+	return odpg_launch_lso(&a, c->stream);
 }
 
 static int ensure_ws(odpg_ctx_t *c, size_t bytes)

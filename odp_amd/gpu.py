@@ -265,6 +265,82 @@ class Gather:
             pass
 
 
+class Lso:
+    """Segmentation plan (include/odpg_lso.h): every frame of a batch cut into
+    segments of header + payload slice with the profile's header updates, on
+    the device. `profiles` is a list of odpg_lso_profile_t (L.lso_profile)."""
+
+    def __init__(self, ctx, profiles, max_pkts):
+        h = C.c_void_p()
+        arr = (L.odpg_lso_profile_t * max(len(profiles), 1))(*profiles)
+        L.check(lib.odpg_lso_create(ctx.h, arr, len(profiles), max_pkts, C.byref(h)),
+                "odpg_lso_create")
+        self.h = h.value
+        self.ctx = ctx
+        self.max_pkts = max_pkts
+
+    def run_dev(self, frames_buf, num, dst_buf, capacity, dst_desc_buf, max_segs, seg_first_buf,
+                status_buf, total_buf, stride=0, desc_buf=None, opt_buf=None, uniform=None):
+        """Asynchronous on the context stream: the segments into dst_buf
+        (capacity bytes) and dst_desc_buf (max_segs entries), seg_first_buf
+        (num + 1 words), status_buf (num bytes), total_buf (odpg_lso_total_t).
+        opt_buf holds num odpg_lso_opt_t; without it `uniform` (an
+        odpg_lso_opt_t) applies to every packet."""
+        s = L.odpg_lso_src_t(frames_buf.ptr, desc_buf.ptr if desc_buf else None, stride, num,
+                             opt_buf.ptr if opt_buf else None, uniform or L.odpg_lso_opt_t())
+        d = L.odpg_lso_dst_t(dst_buf.ptr, capacity, dst_desc_buf.ptr, max_segs, 0,
+                             seg_first_buf.ptr, status_buf.ptr, total_buf.ptr)
+        L.check(lib.odpg_lso(self.h, C.byref(s), C.byref(d)), "odpg_lso")
+
+    def run(self, frames, opts, stride=0, desc=None, capacity=0, max_segs=0, fill=0):
+        """Upload, segment, download (frames, desc, seg_first, status, total).
+        `opts` is an array of LSO_OPT_FIELDS records, one per packet, or one
+        odpg_lso_opt_t for the uniform form. The batch has len(desc) frames,
+        or len(frames) // stride. Every destination buffer is set to the byte
+        `fill` first; frames come back as capacity + 64 bytes, desc with
+        max_segs entries, total as a LSO_TOTAL_FIELDS record."""
+        _, desc_dt = L.np_dtypes()
+        frames = np.ascontiguousarray(frames, dtype=np.uint8)
+        uniform = opts if isinstance(opts, L.odpg_lso_opt_t) else None
+        if desc is not None:
+            desc = np.ascontiguousarray(desc, dtype=desc_dt)
+        num = len(desc) if desc is not None else len(frames) // stride
+        src = [frames, desc,
+               None if uniform else np.ascontiguousarray(opts, dtype=np.dtype(L.LSO_OPT_FIELDS))]
+        fb, db, ob = (None if a is None else self.ctx.buffer(a.nbytes + 64) for a in src)
+        for b, a in zip((fb, db, ob), src):
+            if b:
+                b.upload(a)
+        sizes = (capacity + 64, 8 * max_segs, 4 * (num + 1), num, 24)
+        out = [self.ctx.buffer(n) for n in sizes]
+        for b in out:
+            L.check(lib.odpg_memset_dev(self.ctx.h, b.ptr, fill, b.nbytes), "memset")
+        self.run_dev(fb, num, out[0], capacity, out[1], max_segs, out[2], out[3], out[4], stride,
+                     db, ob, uniform)
+        self.ctx.sync()
+        res = (out[0].download(np.uint8, capacity + 64), out[1].download(desc_dt, max_segs),
+               out[2].download(np.uint32, num + 1), out[3].download(np.uint8, num),
+               out[4].download(np.dtype(L.LSO_TOTAL_FIELDS), 1)[0])
+        for b in (fb, db, ob, *out):
+            if b:
+                b.free()
+        return res
+
+    def close(self):
+        if self.h:
+            # valid after the context's destroy too (odpg.h "object lifetimes")
+            lib.odpg_lso_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        if sys.is_finalizing():   # the HIP runtime may be torn down already
+            return
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Context:
     def __init__(self, device=0, stream=None):
         n = lib.odpg_device_count()
@@ -309,6 +385,9 @@ class Context:
 
     def gather(self, max_pkts=1 << 20):
         return Gather(self, max_pkts)
+
+    def lso(self, profiles, max_pkts=1 << 16):
+        return Lso(self, profiles, max_pkts)
 
     def classify_dev(self, table, frames_buf, num, stride=0, desc_buf=None, opt=0,
                      layer=L.LAYER_ALL, classify=True, out_buf=None, mark_buf=None,
