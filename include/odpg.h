@@ -241,7 +241,27 @@ int         odpg_device_count(void);
  * its device only. */
 int  odpg_ctx_create(int device, void *stream, odpg_ctx_t **ctx);
 void odpg_ctx_destroy(odpg_ctx_t *ctx);
+/* Launch lanes. A context that created its own stream runs verdict-only
+ * odpg_classify launches (res->stats and res->counters NULL) on two streams,
+ * alternately, so that one launch's workgroups fill the compute units the
+ * previous launch's last waves leave. The contract does not change:
+ *   - results are as if the launches ran in call order: a launch that reads
+ *     or writes bytes an earlier launch writes, or writes bytes it reads,
+ *     runs after it (the library tracks the frame / descriptor / out / mark /
+ *     meta ranges of the launches in flight);
+ *   - every other call on the context (counted and stats launches, copies,
+ *     fences, events, odpg_ctx_sync, table updates, odpg_deliver / gather /
+ *     lso / l3fwd / tx_prepare, ...) is ordered after all earlier launches,
+ *     and later launches after it.
+ * odpg_ctx_lanes() is 2 for such a context and 1 for a context on a caller's
+ * stream. odpg_ctx_stream() hands the raw context stream out: the caller may
+ * then enqueue work the library cannot see, so the context joins its lanes
+ * and keeps to one from then on. odpg_ctx_set_lanes(ctx, 1 | 2) switches
+ * the second lane off or on again (-EPERM where the context cannot have
+ * two). */
 void *odpg_ctx_stream(odpg_ctx_t *ctx);
+int  odpg_ctx_lanes(odpg_ctx_t *ctx);
+int  odpg_ctx_set_lanes(odpg_ctx_t *ctx, int lanes);
 /* Kernel strategy: 0 = auto (hash walk for tables of single-word compares
  * with at most 8 distinct (field, mask) groups; evaluate-all for other such
  * tables up to 1024 PMRs; the hybrid hash walk for tables where at most half
@@ -285,8 +305,9 @@ int  odpg_counters_match(const odpg_counters_t *cnt, const odpg_table_t *tbl);
 /* Synchronous: words has ODPG_COUNTER_WORDS(odpg_table_num_cos(tbl)) entries. */
 int  odpg_counters_fold(odpg_counters_t *cnt, uint64_t *words);
 
-/* Device-resident batch: frames/desc/results all in HBM. Asynchronous on the
- * context stream. */
+/* Device-resident batch: frames/desc/results all in HBM. Asynchronous, in
+ * call order on the context ("launch lanes" above: a verdict-only launch may
+ * overlap the previous one where they touch different memory). */
 int odpg_classify(odpg_ctx_t *ctx, const odpg_table_t *tbl,
 		  const odpg_batch_t *batch, const odpg_result_t *res);
 

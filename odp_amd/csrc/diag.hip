@@ -16,6 +16,9 @@
 
 #include "../../include/odpg.h"
 
+/* runtime.hip: the context stream, ordered after both launch lanes */
+extern "C" void *odpg_ctx_stream_joined(odpg_ctx_t *ctx);
+
 #define DBLOCK 256
 
 typedef unsigned int d_u32x4 __attribute__((ext_vector_type(4)));
@@ -116,7 +119,7 @@ extern "C" int odpg_diag_stream(odpg_ctx_t *ctx, const void *src, uint32_t npkt,
 		return -EINVAL;
 	if (npkt == 0)
 		return 0;
-	hipStream_t s = (hipStream_t)odpg_ctx_stream(ctx);
+	hipStream_t s = (hipStream_t)odpg_ctx_stream_joined(ctx);
 	const uint32_t ntiles = (npkt + DBLOCK - 1) / DBLOCK;
 
 	if (grid == 0 || grid > ntiles)

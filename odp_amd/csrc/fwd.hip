@@ -789,7 +789,7 @@ extern "C" int odpg_l3fwd(odpg_ctx_t *ctx, const odpg_fwd_t *f, const odpg_fwd_b
 		return -EINVAL;
 	if (b->num == 0)
 		return 0;
-	hipStream_t s = (hipStream_t)odpg_ctx_stream(ctx);
+	hipStream_t s = (hipStream_t)odpg_ctx_stream_joined(ctx);
 	const uint32_t grid = (b->num + FBLOCK - 1) / FBLOCK;
 	const uint32_t layer = b->error_check ? LAYER_ALL : LAYER_L4;
 

@@ -445,6 +445,10 @@ extern "C" {
 #endif
 void odpg_ctx_ref(struct odpg_ctx_s *ctx);
 void odpg_ctx_unref(struct odpg_ctx_s *ctx);
+/* the context stream ordered after every launch on either lane (runtime.hip
+ * "launch lanes"); unlike the public odpg_ctx_stream() the context keeps
+ * its lanes */
+void *odpg_ctx_stream_joined(struct odpg_ctx_s *ctx);
 #ifdef __cplusplus
 }
 #endif

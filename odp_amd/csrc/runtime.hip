@@ -22,6 +22,7 @@
 #include "deliver.h"
 #include "gather.h"
 #include "lso.h"
+#include "lanes.h"
 
 
 extern "C" int odpg_launch_classify(const odpg_launch_args *a, hipStream_t s);
@@ -49,6 +50,13 @@ struct odpg_ctx_s {
 	hipStream_t stream;
 	bool own_stream;
 	hipStream_t copy_stream;
+	/* launch lanes (lanes.h): lane 0 is `stream`, lane 1 `lane1`; verdict-only
+	 * launches alternate between them, every other use of the context stream
+	 * goes through ctx_stream() / ctx_stream_locked(), which join first */
+	hipStream_t lane1;
+	hipEvent_t lane_ev[2][LANE_NEV];
+	lane_state ls;
+	bool handed_out;   /* odpg_ctx_stream() gave the raw stream away: one lane for good */
 	void *ws;          /* per-workgroup counter partials */
 	uint64_t *sred;    /* stats_commit scratch (SRED_BYTES, kept zeroed) */
 	Stage stage[NSTAGE];
@@ -165,6 +173,48 @@ static uint64_t table_qsig(const odpg_table_t *t)
 	return h;
 }
 
+/* the events and stream waits lanes.h decided, in order */
+static int lane_apply(odpg_ctx_t *c, const lane_act *acts, int n)
+{
+	for (int i = 0; i < n; i++) {
+		const lane_act &a = acts[i];
+		hipStream_t own = a.lane ? c->lane1 : c->stream;
+		hipStream_t other = a.lane ? c->stream : c->lane1;
+		hipEvent_t e = c->lane_ev[a.lane][a.slot];
+		const hipError_t rc = a.op == LANE_RECORD ? hipEventRecord(e, own)
+							  : hipStreamWaitEvent(other, e, 0);
+
+		if (rc != hipSuccess) {
+			fprintf(stderr, "odpg: lane %s failed: %s\n",
+				a.op == LANE_RECORD ? "event record" : "stream wait",
+				hipGetErrorString(rc));
+			return -EIO;
+		}
+	}
+	return 0;
+}
+
+/* The context stream for anything but a verdict-only launch: ordered after
+ * every launch already enqueued on either lane (c->lock held). */
+static hipStream_t ctx_stream_locked(odpg_ctx_t *c)
+{
+	if (c->lane1) {
+		lane_act acts[LANE_MAX_ACTS];
+		int n;
+
+		lane_join(&c->ls, acts, &n);
+		lane_apply(c, acts, n);
+	}
+	return c->stream;
+}
+
+static hipStream_t ctx_stream(odpg_ctx_t *c)
+{
+	std::lock_guard<std::mutex> g(c->lock);
+
+	return ctx_stream_locked(c);
+}
+
 #define HIPCHK(x)                                                              \
 	do {                                                                   \
 		hipError_t e_ = (x);                                           \
@@ -210,6 +260,9 @@ int odpg_ctx_create(int device, void *stream, odpg_ctx_t **out)
 	c->ws = nullptr;
 	c->ws_bytes = 0;
 	c->kernel_mode = 0;
+	c->lane1 = nullptr;
+	c->handed_out = false;
+	lane_init(&c->ls, 1);
 	c->refs.store(1);
 	if (hipSetDevice(device) != hipSuccess) {
 		delete c;
@@ -224,6 +277,19 @@ int odpg_ctx_create(int device, void *stream, odpg_ctx_t **out)
 			return -EIO;
 		}
 		c->own_stream = true;
+		/* the second lane: with the copy stream, three streams a context */
+		if (hipStreamCreateWithFlags(&c->lane1, hipStreamNonBlocking) != hipSuccess) {
+			hipStreamDestroy(c->stream);
+			delete c;
+			return -EIO;
+		}
+		for (int l = 0; l < 2; l++)
+			for (int k = 0; k < LANE_NEV; k++)
+				if (hipEventCreateWithFlags(&c->lane_ev[l][k], hipEventDisableTiming) != hipSuccess) {
+					delete c;
+					return -EIO;
+				}
+		lane_init(&c->ls, 2);
 	}
 	if (hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking) != hipSuccess) {
 		delete c;
@@ -254,6 +320,8 @@ static void ctx_free(odpg_ctx_t *c)
 {
 	hipSetDevice(c->device);
 	hipStreamSynchronize(c->stream);
+	if (c->lane1)
+		hipStreamSynchronize(c->lane1);
 	hipStreamSynchronize(c->copy_stream);
 	if (c->ws)
 		hipFree(c->ws);
@@ -267,6 +335,12 @@ static void ctx_free(odpg_ctx_t *c)
 	for (int k = 0; k < NUM_EVENTS; k++)
 		hipEventDestroy(c->ev[k]);
 	hipStreamDestroy(c->copy_stream);
+	if (c->lane1) {
+		for (int l = 0; l < 2; l++)
+			for (int k = 0; k < LANE_NEV; k++)
+				hipEventDestroy(c->lane_ev[l][k]);
+		hipStreamDestroy(c->lane1);
+	}
 	if (c->own_stream)
 		hipStreamDestroy(c->stream);
 	delete c;
@@ -303,14 +377,59 @@ int odpg_ctx_set_kernel_mode(odpg_ctx_t *c, int mode)
 
 void *odpg_ctx_stream(odpg_ctx_t *c)
 {
-	return c ? (void *)c->stream : nullptr;
+	if (!c)
+		return nullptr;
+	/* the caller may enqueue work the library cannot see: one lane from here on */
+	std::lock_guard<std::mutex> g(c->lock);
+
+	if (c->lane1) {
+		lane_act acts[LANE_MAX_ACTS];
+		int n;
+
+		lane_set(&c->ls, 1, acts, &n);
+		lane_apply(c, acts, n);
+	}
+	c->handed_out = true;
+	return (void *)c->stream;
+}
+
+/* fwd.hip, tx.hip, diag.hip: the context stream, joined, lanes kept */
+void *odpg_ctx_stream_joined(odpg_ctx_t *c)
+{
+	return (void *)ctx_stream(c);
+}
+
+int odpg_ctx_lanes(odpg_ctx_t *c)
+{
+	if (!c)
+		return -EINVAL;
+	std::lock_guard<std::mutex> g(c->lock);
+
+	return c->ls.lanes;
+}
+
+int odpg_ctx_set_lanes(odpg_ctx_t *c, int lanes)
+{
+	if (!c || (lanes != 1 && lanes != 2))
+		return -EINVAL;
+	std::lock_guard<std::mutex> g(c->lock);
+
+	if (lanes == c->ls.lanes)
+		return 0;
+	if (lanes == 2 && (!c->lane1 || c->handed_out))
+		return -EPERM;   /* a caller's stream, or the stream was handed out */
+	lane_act acts[LANE_MAX_ACTS];
+	int n;
+
+	lane_set(&c->ls, lanes, acts, &n);
+	return lane_apply(c, acts, n);
 }
 
 int odpg_ctx_sync(odpg_ctx_t *c)
 {
 	if (!c)
 		return -EINVAL;
-	HIPCHK(hipStreamSynchronize(c->stream));
+	HIPCHK(hipStreamSynchronize(ctx_stream(c)));
 	return 0;
 }
 
@@ -364,9 +483,11 @@ static int table_upload(odpg_ctx_t *c, odpg_table_t *t, odpg_table_t **out)
 		return -ENOMEM;
 	}
 	t->cap = t->hdr.blob_bytes;
+	hipStream_t cs = ctx_stream(c);
+
 	if (hipMemcpyAsync(t->dblob, t->blob.data(), t->hdr.blob_bytes, hipMemcpyHostToDevice,
-			   c->stream) != hipSuccess ||
-	    hipStreamSynchronize(c->stream) != hipSuccess) {
+			   cs) != hipSuccess ||
+	    hipStreamSynchronize(cs) != hipSuccess) {
 		hipFree(t->dblob);
 		delete t;
 		return -EIO;
@@ -436,7 +557,7 @@ int odpg_table_update(odpg_ctx_t *c, odpg_table_t *t, const odpg_rules_t *rules)
 		void *nb = nullptr;
 
 		/* launches still reading the old allocation end first */
-		if (hipStreamSynchronize(c->stream) != hipSuccess ||
+		if (hipStreamSynchronize(ctx_stream_locked(c)) != hipSuccess ||
 		    hipMalloc(&nb, hdr.blob_bytes) != hipSuccess)
 			return -ENOMEM;
 		hipFree(t->dblob);
@@ -448,9 +569,11 @@ int odpg_table_update(odpg_ctx_t *c, odpg_table_t *t, const odpg_rules_t *rules)
 	t->cycle = odpg_rules_has_cycle(t->blob, t->hdr);
 	t->depth = table_walk_depth(t);
 	t->qsig = table_qsig(t);
+	hipStream_t cs = ctx_stream_locked(c);
+
 	if (hipMemcpyAsync(t->dblob, t->blob.data(), t->hdr.blob_bytes, hipMemcpyHostToDevice,
-			   c->stream) != hipSuccess ||
-	    hipEventRecord(t->uploaded, c->stream) != hipSuccess)
+			   cs) != hipSuccess ||
+	    hipEventRecord(t->uploaded, cs) != hipSuccess)
 		return -EIO;
 	return 0;
 }
@@ -569,12 +692,13 @@ int odpg_counters_create(odpg_ctx_t *c, const odpg_table_t *t, odpg_counters_t *
 	}
 	{
 		std::lock_guard<std::mutex> g(c->lock);
+		hipStream_t cs = ctx_stream_locked(c);
 
-		if (hipMemsetAsync(k->drows, 0, rb, c->stream) != hipSuccess ||
-		    hipMemsetAsync(k->dsum, 0, (size_t)k->words * 8u, c->stream) != hipSuccess ||
+		if (hipMemsetAsync(k->drows, 0, rb, cs) != hipSuccess ||
+		    hipMemsetAsync(k->dsum, 0, (size_t)k->words * 8u, cs) != hipSuccess ||
 		    hipMemcpyAsync(k->dqcol, k->qcol.data(), (size_t)(k->ncos + 1u) * 4u,
-				   hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-		    hipEventRecord(k->done, c->stream) != hipSuccess) {
+				   hipMemcpyHostToDevice, cs) != hipSuccess ||
+		    hipEventRecord(k->done, cs) != hipSuccess) {
 			counters_free(k);
 			return -EIO;
 		}
@@ -597,7 +721,7 @@ void odpg_counters_destroy(odpg_counters_t *k)
 	if (!k)
 		return;
 	hipSetDevice(k->ctx->device);
-	hipStreamSynchronize(k->ctx->stream);   /* launches still adding into the rows */
+	hipStreamSynchronize(ctx_stream(k->ctx));   /* launches still adding into the rows */
 	counters_free(k);
 }
 
@@ -612,12 +736,13 @@ int odpg_counters_fold(odpg_counters_t *k, uint64_t *words)
 	{
 		/* enqueue behind every launch already on the context stream */
 		std::lock_guard<std::mutex> g(c->lock);
+		hipStream_t cs = ctx_stream_locked(c);
 
-		if (odpg_launch_counters_fold(k->drows, k->rows, k->words, k->dsum, c->stream) ||
+		if (odpg_launch_counters_fold(k->drows, k->rows, k->words, k->dsum, cs) ||
 		    hipMemcpyAsync(k->hsum, k->dsum, (size_t)k->words * 8u, hipMemcpyDeviceToHost,
-				   c->stream) != hipSuccess ||
-		    hipMemsetAsync(k->dsum, 0, (size_t)k->words * 8u, c->stream) != hipSuccess ||
-		    hipEventRecord(k->done, c->stream) != hipSuccess)
+				   cs) != hipSuccess ||
+		    hipMemsetAsync(k->dsum, 0, (size_t)k->words * 8u, cs) != hipSuccess ||
+		    hipEventRecord(k->done, cs) != hipSuccess)
 			return -EIO;
 	}
 	HIPCHK(hipEventSynchronize(k->done));
@@ -687,13 +812,14 @@ int odpg_deliver_create(odpg_ctx_t *c, const odpg_table_t *t, uint32_t max_pkts,
 		      hipMalloc(&a.pairs, std::max<size_t>(max_pkts, 1u) * 8u) == hipSuccess)) &&
 	    hipEventCreateWithFlags(&ready, hipEventDisableTiming) == hipSuccess) {
 		std::lock_guard<std::mutex> g(c->lock);
+		hipStream_t cs = ctx_stream_locked(c);
 
 		rc = -EIO;
 		if (hipMemcpyAsync((void *)a.qbase, d->qcol.data(), qb, hipMemcpyHostToDevice,
-				   c->stream) == hipSuccess &&
-		    odpg_launch_deliver_clear(a.dtotal, DLV_RADIX, c->stream) == 0 &&
-		    (!two || odpg_launch_deliver_clear(a.bcount, a.nbuckets, c->stream) == 0) &&
-		    hipEventRecord(ready, c->stream) == hipSuccess)
+				   cs) == hipSuccess &&
+		    odpg_launch_deliver_clear(a.dtotal, DLV_RADIX, cs) == 0 &&
+		    (!two || odpg_launch_deliver_clear(a.bcount, a.nbuckets, cs) == 0) &&
+		    hipEventRecord(ready, cs) == hipSuccess)
 			rc = 0;
 	}
 	/* the upload reads d->qcol: done before the plan is handed out */
@@ -714,7 +840,7 @@ void odpg_deliver_destroy(odpg_deliver_t *d)
 	if (!d)
 		return;
 	hipSetDevice(d->ctx->device);
-	hipStreamSynchronize(d->ctx->stream);   /* launches still using the workspace */
+	hipStreamSynchronize(ctx_stream(d->ctx));   /* launches still using the workspace */
 	deliver_free(d);
 }
 
@@ -757,7 +883,7 @@ int odpg_deliver(odpg_deliver_t *d, const odpg_out_t *out, uint32_t num, uint32_
 	hipSetDevice(c->device);
 	std::lock_guard<std::mutex> g(c->lock);
 
-	return odpg_launch_deliver(&a, c->stream);
+	return odpg_launch_deliver(&a, ctx_stream_locked(c));
 }
 
 /* ---- dense queue batches (odpg_gather.h; kernels in gather.hip) ----------- */
@@ -804,7 +930,7 @@ void odpg_gather_destroy(odpg_gather_t *g)
 	if (!g)
 		return;
 	hipSetDevice(g->ctx->device);
-	hipStreamSynchronize(g->ctx->stream);   /* launches still using the workspace */
+	hipStreamSynchronize(ctx_stream(g->ctx));   /* launches still using the workspace */
 	gather_free(g);
 }
 
@@ -824,7 +950,7 @@ int odpg_gather(odpg_gather_t *g, const odpg_gather_src_t *src, const uint32_t *
 	hipSetDevice(c->device);
 	std::lock_guard<std::mutex> lk(c->lock);
 
-	return odpg_launch_gather(&a, c->stream);
+	return odpg_launch_gather(&a, ctx_stream_locked(c));
 }
 
 /* ---- segmentation offload (odpg_lso.h; kernels in lso.hip) ----------------- */
@@ -911,7 +1037,7 @@ void odpg_lso_destroy(odpg_lso_t *l)
 	if (!l)
 		return;
 	hipSetDevice(l->ctx->device);
-	hipStreamSynchronize(l->ctx->stream);   /* launches still using the workspace */
+	hipStreamSynchronize(ctx_stream(l->ctx));   /* launches still using the workspace */
 	lso_free(l);
 }
 
@@ -929,7 +1055,7 @@ int odpg_lso(odpg_lso_t *l, const odpg_lso_src_t *src, const odpg_lso_dst_t *dst
 	hipSetDevice(c->device);
 	std::lock_guard<std::mutex> lk(c->lock);
 
-	return odpg_launch_lso(&a, c->stream);
+	return odpg_launch_lso(&a, ctx_stream_locked(c));
 }
 
 static int ensure_ws(odpg_ctx_t *c, size_t bytes)
@@ -937,7 +1063,7 @@ static int ensure_ws(odpg_ctx_t *c, size_t bytes)
 	if (c->ws_bytes >= bytes)
 		return 0;
 	if (c->ws) {
-		HIPCHK(hipStreamSynchronize(c->stream));
+		HIPCHK(hipStreamSynchronize(ctx_stream_locked(c)));
 		HIPCHK(hipFree(c->ws));
 		c->ws = nullptr;
 		c->ws_bytes = 0;
@@ -1104,7 +1230,7 @@ static int ensure_stage(odpg_ctx_t *c, size_t span, uint32_t chunk, bool desc, b
 
 	if (c->stage_span < span + 16 || c->stage_chunk < chunk ||
 	    (c->stage_flags & want) != want) {
-		HIPCHK(hipStreamSynchronize(c->stream));
+		HIPCHK(hipStreamSynchronize(ctx_stream_locked(c)));
 		HIPCHK(hipStreamSynchronize(c->copy_stream));
 		const size_t nspan = span + 16 > c->stage_span ? span + 16 : c->stage_span;
 		const uint32_t nchunk = chunk > c->stage_chunk ? chunk : c->stage_chunk;
@@ -1130,7 +1256,7 @@ static int ensure_stage(odpg_ctx_t *c, size_t span, uint32_t chunk, bool desc, b
 		c->stage_flags = flags;
 	}
 	if (nstats > c->stage_nstats) {
-		HIPCHK(hipStreamSynchronize(c->stream));
+		HIPCHK(hipStreamSynchronize(ctx_stream_locked(c)));
 		hipFree(c->stage_stats);
 		c->stage_stats = nullptr;
 		c->stage_nstats = 0;
@@ -1186,7 +1312,32 @@ int odpg_classify(odpg_ctx_t *c, const odpg_table_t *t, const odpg_batch_t *b,
 	hipSetDevice(c->device);
 	if ((rc = ensure_ws(c, ws_need(t, b->num, r->stats != nullptr))))
 		return rc;
-	return classify_on(c, c->stream, t, b, r, c->ws);
+	if (r->stats || r->counters || c->ls.lanes != 2)
+		/* counted launches add into workgroup-owned rows with plain
+		 * read-modify-writes and stats launches share the context's
+		 * scratch: both stay in order on the context stream */
+		return classify_on(c, ctx_stream_locked(c), t, b, r, c->ws);
+	/* verdict-only: the next lane, behind whatever on the other lane touches
+	 * the same bytes (lanes.h). Descriptor batches bound their frame bytes by
+	 * the descriptor format (32-bit offset + 32-bit length) */
+	const uintptr_t f = (uintptr_t)b->frames, o = (uintptr_t)r->out;
+	lane_access acc = {};
+	lane_act acts[LANE_MAX_ACTS];
+	int n;
+
+	acc.rd[0] = {f, f + (b->desc ? (uintptr_t)2 << 32 : (uintptr_t)b->num * b->stride)};
+	if (b->desc)
+		acc.rd[1] = {(uintptr_t)b->desc, (uintptr_t)b->desc + (uintptr_t)b->num * sizeof(odpg_desc_t)};
+	acc.wr[0] = {o, o + (uintptr_t)b->num * sizeof(odpg_out_t)};
+	if (r->mark)
+		acc.wr[1] = {(uintptr_t)r->mark, (uintptr_t)r->mark + (uintptr_t)b->num * 2u};
+	if (r->meta)
+		acc.wr[2] = {(uintptr_t)r->meta, (uintptr_t)r->meta + (uintptr_t)b->num * sizeof(odpg_meta_t)};
+	const int lane = lane_launch(&c->ls, &acc, acts, &n);
+
+	if (lane_apply(c, acts, n))
+		return -EIO;
+	return classify_on(c, lane ? c->lane1 : c->stream, t, b, r, c->ws);
 }
 
 /* Host-buffer path: frames/desc/results in host memory (pinned is fastest).
@@ -1214,6 +1365,8 @@ int odpg_classify_host(odpg_ctx_t *c, const odpg_table_t *t, const odpg_batch_t 
 	std::lock_guard<std::mutex> g(c->lock);
 
 	hipSetDevice(c->device);
+	/* the lock is held to the end: no launch moves to the other lane meanwhile */
+	hipStream_t cs = ctx_stream_locked(c);
 
 	/* size the frame staging buffers */
 	size_t max_span = 0;
@@ -1252,7 +1405,7 @@ int odpg_classify_host(odpg_ctx_t *c, const odpg_table_t *t, const odpg_batch_t 
 	if ((err = ensure_stage(c, max_span, chunk, b->desc != nullptr, r->mark != nullptr,
 				r->meta != nullptr, r->stats ? nstats : 0u)))
 		return err;
-	if (r->stats && hipMemsetAsync(c->stage_stats, 0, nstats * 8u, c->stream) != hipSuccess)
+	if (r->stats && hipMemsetAsync(c->stage_stats, 0, nstats * 8u, cs) != hipSuccess)
 		return -EIO;
 	err = ensure_ws(c, ws_need(t, chunk, r->stats != nullptr));
 
@@ -1288,7 +1441,7 @@ int odpg_classify_host(odpg_ctx_t *c, const odpg_table_t *t, const odpg_batch_t 
 			}
 		}
 		hipEventRecord(B.h2d_done, c->copy_stream);
-		hipStreamWaitEvent(c->stream, B.h2d_done, 0);
+		hipStreamWaitEvent(cs, B.h2d_done, 0);
 
 		odpg_batch_t cb = *b;
 		odpg_result_t cr;
@@ -1301,32 +1454,32 @@ int odpg_classify_host(odpg_ctx_t *c, const odpg_table_t *t, const odpg_batch_t 
 		cr.meta = r->meta ? B.meta : nullptr;
 		cr.stats = r->stats ? c->stage_stats : nullptr;
 		cr.counters = r->counters;
-		if (classify_on(c, c->stream, t, &cb, &cr, c->ws)) {
+		if (classify_on(c, cs, t, &cb, &cr, c->ws)) {
 			err = -EIO;
 			break;
 		}
 		hipMemcpyAsync(r->out + first, B.out, (size_t)n * sizeof(odpg_out_t),
-			       hipMemcpyDeviceToHost, c->stream);
+			       hipMemcpyDeviceToHost, cs);
 		if (r->mark)
 			hipMemcpyAsync(r->mark + first, B.mark, (size_t)n * 2u, hipMemcpyDeviceToHost,
-				       c->stream);
+				       cs);
 		if (r->meta)
 			hipMemcpyAsync(r->meta + first, B.meta, (size_t)n * sizeof(odpg_meta_t),
-				       hipMemcpyDeviceToHost, c->stream);
-		hipEventRecord(B.compute_done, c->stream);
+				       hipMemcpyDeviceToHost, cs);
+		hipEventRecord(B.compute_done, cs);
 	}
 	if (!err && r->stats) {
 		std::vector<uint64_t> hs(nstats);
 
 		if (hipMemcpyAsync(hs.data(), c->stage_stats, nstats * 8u, hipMemcpyDeviceToHost,
-				   c->stream) != hipSuccess ||
-		    hipStreamSynchronize(c->stream) != hipSuccess)
+				   cs) != hipSuccess ||
+		    hipStreamSynchronize(cs) != hipSuccess)
 			err = -EIO;
 		else
 			for (uint32_t k = 0; k < nstats; k++)
 				r->stats[k] += hs[k];
 	}
-	if (hipStreamSynchronize(c->stream) != hipSuccess ||
+	if (hipStreamSynchronize(cs) != hipSuccess ||
 	    hipStreamSynchronize(c->copy_stream) != hipSuccess)
 		err = err ? err : -EIO;
 	return err;
@@ -1347,6 +1500,7 @@ int odpg_dev_free(odpg_ctx_t *c, void *ptr)
 	if (!c)
 		return -EINVAL;
 	hipSetDevice(c->device);
+	ctx_stream(c);     /* a join, as for every call on the context */
 	HIPCHK(hipFree(ptr));
 	return 0;
 }
@@ -1381,8 +1535,10 @@ int odpg_memcpy_h2d(odpg_ctx_t *c, void *dst, const void *src, size_t bytes)
 {
 	if (!c)
 		return -EINVAL;
-	HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
-	HIPCHK(hipStreamSynchronize(c->stream));
+	hipStream_t cs = ctx_stream(c);
+
+	HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, cs));
+	HIPCHK(hipStreamSynchronize(cs));
 	return 0;
 }
 
@@ -1390,8 +1546,10 @@ int odpg_memcpy_d2h(odpg_ctx_t *c, void *dst, const void *src, size_t bytes)
 {
 	if (!c)
 		return -EINVAL;
-	HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
-	HIPCHK(hipStreamSynchronize(c->stream));
+	hipStream_t cs = ctx_stream(c);
+
+	HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, cs));
+	HIPCHK(hipStreamSynchronize(cs));
 	return 0;
 }
 
@@ -1399,7 +1557,7 @@ int odpg_memset_dev(odpg_ctx_t *c, void *dst, int value, size_t bytes)
 {
 	if (!c)
 		return -EINVAL;
-	HIPCHK(hipMemsetAsync(dst, value, bytes, c->stream));
+	HIPCHK(hipMemsetAsync(dst, value, bytes, ctx_stream(c)));
 	return 0;
 }
 
@@ -1407,7 +1565,7 @@ int odpg_event_record(odpg_ctx_t *c, int slot)
 {
 	if (!c || slot < 0 || slot >= NUM_EVENTS)
 		return -EINVAL;
-	HIPCHK(hipEventRecord(c->ev[slot], c->stream));
+	HIPCHK(hipEventRecord(c->ev[slot], ctx_stream(c)));
 	return 0;
 }
 
@@ -1441,7 +1599,7 @@ int odpg_fence_record(odpg_ctx_t *c, odpg_fence_t *f)
 {
 	if (!c || !f || f->device != c->device)
 		return -EINVAL;
-	HIPCHK(hipEventRecord(f->ev, c->stream));
+	HIPCHK(hipEventRecord(f->ev, ctx_stream(c)));
 	return 0;
 }
 

@@ -581,7 +581,7 @@ extern "C" int odpg_tx_prepare(odpg_ctx_t *ctx, const odpg_tx_batch_t *b,
 	A.num_qs = cfg->num_qs;
 	A.index = cfg->index;
 	A.out = out;
-	hipStream_t s = (hipStream_t)odpg_ctx_stream(ctx);
+	hipStream_t s = (hipStream_t)odpg_ctx_stream_joined(ctx);
 
 	if (b->stride == 64u && !b->desc && !b->meta && b->num < (1u << 30)) {
 		const uint32_t want = ((b->num + 63u) / 64u + TX_BLOCK / 64u - 1u) / (TX_BLOCK / 64u);
