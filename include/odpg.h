@@ -231,11 +231,11 @@ int         odpg_device_count(void);
  *
  * Object lifetimes: tables, counters, forwarders (odpg_fwd.h), delivery
  * plans (odpg_deliver.h), gather plans (odpg_gather.h), segmentation plans
- * (odpg_lso.h) and fences may be destroyed in any order relative to each
+ * (odpg_lso.h), reassembly plans (odpg_reass.h) and fences may be destroyed in any order relative to each
  * other and to their context.
  * odpg_ctx_destroy() releases the caller's handle and the odp_cls bindings
- * made on the context; counters, forwarders, delivery, gather and
- * segmentation plans and fences created on it hold a reference, and the
+ * made on the context; counters, forwarders, delivery, gather,
+ * segmentation and reassembly plans and fences created on it hold a reference, and the
  * context's stream and device memory are freed when the last of them is destroyed (the context
  * handle itself may not be used after odpg_ctx_destroy). A table refers to
  * its device only. */
@@ -251,7 +251,7 @@ void odpg_ctx_destroy(odpg_ctx_t *ctx);
  *     meta ranges of the launches in flight);
  *   - every other call on the context (counted and stats launches, copies,
  *     fences, events, odpg_ctx_sync, table updates, odpg_deliver / gather /
- *     lso / l3fwd / tx_prepare, ...) is ordered after all earlier launches,
+ *     lso / reass / l3fwd / tx_prepare, ...) is ordered after all earlier launches,
  *     and later launches after it.
  * odpg_ctx_lanes() is 2 for such a context and 1 for a context on a caller's
  * stream. odpg_ctx_stream() hands the raw context stream out: the caller may

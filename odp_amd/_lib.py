@@ -246,6 +246,33 @@ def lso_profile(proto, fields=()):
     return p
 
 
+# ---- include/odpg_reass.h ---------------------------------------------------
+REASS_TILE = 64          # ODPG_REASS_TILE: packets one copy workgroup handles
+REASS_WHOLE, REASS_JOINED, REASS_HELD, REASS_BAD = range(4)
+
+
+class odpg_reass_src_t(C.Structure):
+    _fields_ = [("frames", C.c_void_p), ("desc", C.c_void_p), ("stride", C.c_uint32),
+                ("num", C.c_uint32), ("l3_offset", C.c_void_p), ("l3_stride", C.c_uint32),
+                ("uniform_l3", C.c_uint16), ("reserved", C.c_uint16)]
+
+
+class odpg_reass_total_t(C.Structure):
+    _fields_ = [("num_out", C.c_uint32), ("copied", C.c_uint32), ("num_held", C.c_uint32),
+                ("num_bad", C.c_uint32), ("bytes", C.c_uint64)]
+
+
+class odpg_reass_dst_t(C.Structure):
+    _fields_ = [("frames", C.c_void_p), ("capacity", C.c_uint64), ("desc", C.c_void_p),
+                ("max_out", C.c_uint32), ("reserved", C.c_uint32), ("origin", C.c_void_p),
+                ("status", C.c_void_p), ("held", C.c_void_p), ("held_offsets", C.c_void_p),
+                ("total", C.c_void_p)]
+
+
+REASS_TOTAL_FIELDS = [("num_out", "<u4"), ("copied", "<u4"), ("num_held", "<u4"),
+                      ("num_bad", "<u4"), ("bytes", "<u8")]                    # 24 B
+
+
 # ---- include/odpg_pcap.h ----------------------------------------------------
 class odpg_capture_t(C.Structure):
     _fields_ = [("frames", C.c_void_p), ("desc", C.c_void_p), ("num", C.c_uint32),
@@ -500,6 +527,10 @@ SIGNATURES = {
     "odpg_lso_create": (_i32, [_vp, C.POINTER(odpg_lso_profile_t), _u32, _u32, C.POINTER(_vp)]),
     "odpg_lso_destroy": (None, [_vp]),
     "odpg_lso": (_i32, [_vp, C.POINTER(odpg_lso_src_t), C.POINTER(odpg_lso_dst_t)]),
+    # include/odpg_reass.h
+    "odpg_reass_create": (_i32, [_vp, _u32, C.POINTER(_vp)]),
+    "odpg_reass_destroy": (None, [_vp]),
+    "odpg_reass": (_i32, [_vp, C.POINTER(odpg_reass_src_t), C.POINTER(odpg_reass_dst_t)]),
     # include/odpg_group.h
     "odpg_group_create": (_i32, [C.POINTER(C.c_int), _u32, C.POINTER(_vp)]),
     "odpg_group_destroy": (None, [_vp]),

@@ -65,6 +65,7 @@
 #include <stdint.h>
 
 #include "lso.h"
+#include "unit_copy.h"   /* funnel, keep_unit, scans, find_from */
 
 namespace {
 
@@ -83,80 +84,6 @@ static_assert(sizeof(odpg_lso_profile_t) == 104 && sizeof(odpg_lso_opt_t) == 8 &
 static_assert(ODPG_LSO_MAX_PAYLOAD_OFFSET + 8u <= 16u * WIN, "window");
 
 typedef odpg_lso_args Args;
-
-__device__ __forceinline__ uint32_t units_of(uint32_t len)
-{
-	return (uint32_t)(((uint64_t)len + 15u) >> 4);
-}
-
-/* the low `nb` bytes of w (nb <= 0: none, nb >= 4: all) */
-__device__ __forceinline__ uint32_t keep_bytes(uint32_t w, int32_t nb)
-{
-	return nb >= 4 ? w : nb <= 0 ? 0u : w & ((1u << (8 * nb)) - 1u);
-}
-
-__device__ __forceinline__ uint4 keep_unit(uint4 v, int32_t nb)
-{
-	return make_uint4(keep_bytes(v.x, nb), keep_bytes(v.y, nb - 4), keep_bytes(v.z, nb - 8),
-			  keep_bytes(v.w, nb - 12));
-}
-
-/* bytes [sh, sh + 16) of the 32 bytes lo | hi, sh in [0, 16) */
-__device__ __forceinline__ uint4 funnel(uint4 lo, uint4 hi, uint32_t sh)
-{
-	const bool s8 = sh & 8u, s4 = sh & 4u;
-	uint32_t w0 = s8 ? lo.z : lo.x, w1 = s8 ? lo.w : lo.y, w2 = s8 ? hi.x : lo.z;
-	uint32_t w3 = s8 ? hi.y : lo.w, w4 = s8 ? hi.z : hi.x, w5 = s8 ? hi.w : hi.y;
-
-	w0 = s4 ? w1 : w0;
-	w1 = s4 ? w2 : w1;
-	w2 = s4 ? w3 : w2;
-	w3 = s4 ? w4 : w3;
-	w4 = s4 ? w5 : w4;
-	const uint32_t b = sh & 3u;
-
-	return make_uint4(__builtin_amdgcn_alignbyte(w1, w0, b), __builtin_amdgcn_alignbyte(w2, w1, b),
-			  __builtin_amdgcn_alignbyte(w3, w2, b), __builtin_amdgcn_alignbyte(w4, w3, b));
-}
-
-/* inclusive prefix over the 64 lanes of a wave */
-template <typename V>
-__device__ __forceinline__ V wave_incl_scan(V v)
-{
-	const uint32_t lane = threadIdx.x & 63u;
-
-	for (uint32_t off = 1; off < 64u; off <<= 1) {
-		const V t = __shfl_up(v, off);
-
-		if (lane >= off)
-			v += t;
-	}
-	return v;
-}
-
-/* exclusive prefix of v over the workgroup's lanes (ws: one word per wave);
- * *total: the sum over all of them */
-template <uint32_t NW>
-__device__ __forceinline__ uint64_t block_excl_scan(uint64_t v, uint64_t *ws, uint64_t *total)
-{
-	const uint32_t wave = threadIdx.x >> 6;
-	const uint64_t inc = wave_incl_scan(v);
-
-	if ((threadIdx.x & 63u) == 63u)
-		ws[wave] = inc;
-	__syncthreads();
-	uint64_t base = 0, all = 0;
-
-	for (uint32_t w = 0; w < NW; w++) {
-		const uint64_t c = ws[w];
-
-		base += w < wave ? c : 0u;
-		all += c;
-	}
-	__syncthreads();
-	*total = all;
-	return base + inc - v;
-}
 
 __device__ __forceinline__ void stage_profiles(const Args &a, odpg_lso_profile_t *s_prof)
 {
@@ -196,22 +123,6 @@ __device__ __forceinline__ uint32_t seg_len(const Pkt &p, uint32_t k)
 __device__ __forceinline__ const uint8_t *frame_of(const Args &a, const Pkt &p, uint32_t i)
 {
 	return a.src.frames + (a.src.desc ? (uint64_t)p.off : (uint64_t)i * a.src.stride);
-}
-
-/* the first f in [f, T - 1] with arr[f + 1] > x; the caller knows one exists */
-__device__ __forceinline__ uint32_t find_from(const uint32_t *arr, uint32_t f, uint32_t x)
-{
-	uint32_t hi = T - 1u;
-
-	while (f < hi) {
-		const uint32_t mid = (f + hi) >> 1;
-
-		if (arr[mid + 1u] > x)
-			hi = mid;
-		else
-			f = mid + 1u;
-	}
-	return f;
 }
 
 /* ---- launch 1: the rules per packet, tile sums ----------------------------- */
@@ -452,7 +363,7 @@ __global__ __launch_bounds__(WG) void lso_copy(Args a)
 		bool fits = false;
 
 		if (r < nseg) {
-			const uint32_t f = find_from(s_sfirst, 0u, r), k = r - s_sfirst[f];
+			const uint32_t f = find_from(s_sfirst, 0u, r, T - 1u), k = r - s_sfirst[f];
 			const Pkt p = decode(s_pk[f]);
 			const uint32_t seglen = seg_len(p, k), j = S + r;
 			const uint64_t start = (uint64_t)s_ustart[f] + (uint64_t)k * p.su;
@@ -499,7 +410,7 @@ __global__ __launch_bounds__(WG) void lso_copy(Args a)
 				if (u >= nuf)
 					continue;
 				if (u >= hi) {      /* left the packet: u < nuf <= start[T] */
-					f = find_from(s_ustart, f, u);
+					f = find_from(s_ustart, f, u, T - 1u);
 					lo = s_ustart[f];
 					hi = s_ustart[f + 1u];
 					p = decode(s_pk[f]);
@@ -559,7 +470,7 @@ __global__ __launch_bounds__(WG) void lso_copy(Args a)
 		Pkt p = {};
 
 		if (w < nw) {
-			f = find_from(s_wfirst, 0u, w);
+			f = find_from(s_wfirst, 0u, w, T - 1u);
 			k = w - s_wfirst[f];
 			act = s_sfirst[f] + k < nfit;
 		}

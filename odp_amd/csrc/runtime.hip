@@ -22,6 +22,7 @@
 #include "deliver.h"
 #include "gather.h"
 #include "lso.h"
+#include "reass.h"
 #include "lanes.h"
 
 
@@ -1056,6 +1057,107 @@ int odpg_lso(odpg_lso_t *l, const odpg_lso_src_t *src, const odpg_lso_dst_t *dst
 	std::lock_guard<std::mutex> lk(c->lock);
 
 	return odpg_launch_lso(&a, ctx_stream_locked(c));
+}
+
+/* ---- IPv4 reassembly (odpg_reass.h; kernels in reass.hip) ------------------- */
+struct odpg_reass_s {
+	odpg_ctx_t *ctx;
+	uint32_t max_pkts;
+	odpg_reass_pk *pk;             /* device: max_pkts records, each */
+	odpg_reass_grp *grp;
+	uint32_t *lead, *obase;
+	uint32_t *flow;                /* device: pow2 >= 2 max_pkts slots, each */
+	unsigned long long *pos;
+	uint64_t *tunits;              /* device: a word per tile, each */
+	uint32_t *touts, *theld, *tbad;
+};
+
+/* the smallest power of two >= 2 n, at least 64 */
+static uint32_t reass_slots(uint32_t n)
+{
+	uint32_t s = 64;
+
+	while (s < 2u * n)
+		s <<= 1;
+	return s;
+}
+
+static void reass_free(odpg_reass_t *r)
+{
+	odpg_ctx_t *c = r->ctx;
+
+	hipFree(r->pk);
+	hipFree(r->grp);
+	hipFree(r->lead);
+	hipFree(r->obase);
+	hipFree(r->flow);
+	hipFree(r->pos);
+	hipFree(r->tunits);
+	hipFree(r->touts);
+	hipFree(r->theld);
+	hipFree(r->tbad);
+	delete r;
+	odpg_ctx_unref(c);
+}
+
+int odpg_reass_create(odpg_ctx_t *c, uint32_t max_pkts, odpg_reass_t **out)
+{
+	/* a leader's index shares a 64-bit key with a byte position; 2 * 2^24 slots */
+	if (!c || !out || max_pkts > (1u << 24))
+		return -EINVAL;
+	odpg_reass_t *r = new odpg_reass_t();
+	const size_t n = std::max<size_t>(max_pkts, 1u), slots = reass_slots(max_pkts);
+	const size_t tiles = (n + REASS_TILE - 1u) / REASS_TILE;
+
+	r->ctx = c;
+	odpg_ctx_ref(c);
+	r->max_pkts = max_pkts;
+	hipSetDevice(c->device);
+	if (hipMalloc(&r->pk, n * sizeof(odpg_reass_pk)) != hipSuccess ||
+	    hipMalloc(&r->grp, n * sizeof(odpg_reass_grp)) != hipSuccess ||
+	    hipMalloc(&r->lead, n * 4u) != hipSuccess || hipMalloc(&r->obase, n * 4u) != hipSuccess ||
+	    hipMalloc(&r->flow, slots * 4u) != hipSuccess ||
+	    hipMalloc(&r->pos, slots * 8u) != hipSuccess ||
+	    hipMalloc(&r->tunits, tiles * 8u) != hipSuccess ||
+	    hipMalloc(&r->touts, tiles * 4u) != hipSuccess ||
+	    hipMalloc(&r->theld, tiles * 4u) != hipSuccess ||
+	    hipMalloc(&r->tbad, tiles * 4u) != hipSuccess) {
+		reass_free(r);
+		return -ENOMEM;
+	}
+	*out = r;
+	return 0;
+}
+
+void odpg_reass_destroy(odpg_reass_t *r)
+{
+	if (!r)
+		return;
+	hipSetDevice(r->ctx->device);
+	hipStreamSynchronize(ctx_stream(r->ctx));   /* launches still using the workspace */
+	reass_free(r);
+}
+
+int odpg_reass(odpg_reass_t *r, const odpg_reass_src_t *src, const odpg_reass_dst_t *dst)
+{
+	if (!r || !src || !dst || !dst->frames || !dst->status || !dst->held || !dst->held_offsets ||
+	    !dst->total || ((!dst->desc || !dst->origin) && dst->max_out) ||
+	    (!src->frames && src->num) ||
+	    (((uintptr_t)src->frames | (uintptr_t)dst->frames) & 15u) || src->num > r->max_pkts ||
+	    (!src->desc && (!src->stride || (src->stride & 15u))) ||
+	    (src->l3_offset && (((uintptr_t)src->l3_offset & 1u) || !src->l3_stride ||
+				(src->l3_stride & 1u))) ||
+	    dst->capacity > (1ull << 32))
+		return -EINVAL;
+	odpg_ctx_t *c = r->ctx;
+	/* tables sized for this batch: clearing them costs what the batch is worth */
+	odpg_reass_args a = {*src, *dst, r->pk, r->grp, r->lead, r->obase, r->flow, r->pos,
+			     reass_slots(src->num), 0, r->tunits, r->touts, r->theld, r->tbad};
+
+	hipSetDevice(c->device);
+	std::lock_guard<std::mutex> lk(c->lock);
+
+	return odpg_launch_reass(&a, ctx_stream_locked(c));
 }
 
 static int ensure_ws(odpg_ctx_t *c, size_t bytes)

@@ -341,6 +341,86 @@ class Lso:
             pass
 
 
+class Reass:
+    """Reassembly plan (include/odpg_reass.h): the IPv4 fragments of a batch
+    joined into datagrams again on the device, other frames passed through,
+    fragments of incomplete datagrams listed as held."""
+
+    def __init__(self, ctx, max_pkts):
+        h = C.c_void_p()
+        L.check(lib.odpg_reass_create(ctx.h, max_pkts, C.byref(h)), "odpg_reass_create")
+        self.h = h.value
+        self.ctx = ctx
+        self.max_pkts = max_pkts
+
+    def run_dev(self, frames_buf, num, dst_buf, capacity, dst_desc_buf, max_out, origin_buf,
+                status_buf, held_buf, held_offsets_buf, total_buf, stride=0, desc_buf=None,
+                l3_ptr=None, l3_stride=2, uniform_l3=14):
+        """Asynchronous on the context stream: the output frames into dst_buf
+        (capacity bytes), dst_desc_buf and origin_buf (max_out entries),
+        status_buf (num bytes), held_buf (num words), held_offsets_buf (2
+        words), total_buf (odpg_reass_total_t). l3_ptr is the device address
+        of the first u16 L3 offset, the next l3_stride bytes on (for a
+        classify result: meta_buf.ptr + 14 with sizeof(odpg_meta_t));
+        without it uniform_l3 applies to every packet."""
+        s = L.odpg_reass_src_t(frames_buf.ptr, desc_buf.ptr if desc_buf else None, stride, num,
+                               l3_ptr, l3_stride, uniform_l3, 0)
+        d = L.odpg_reass_dst_t(dst_buf.ptr, capacity, dst_desc_buf.ptr, max_out, 0,
+                               origin_buf.ptr, status_buf.ptr, held_buf.ptr,
+                               held_offsets_buf.ptr, total_buf.ptr)
+        L.check(lib.odpg_reass(self.h, C.byref(s), C.byref(d)), "odpg_reass")
+
+    def run(self, frames, l3, stride=0, desc=None, capacity=0, max_out=0, fill=0, l3_stride=2):
+        """Upload, reassemble, download (frames, desc, origin, status, held,
+        held_offsets, total). `l3` is an int (one L3 offset for all) or an
+        array whose bytes hold the u16 offsets l3_stride apart from byte 0.
+        The batch has len(desc) frames, or len(frames) // stride. Every
+        destination buffer is set to the byte `fill` first; frames come back
+        as capacity + 64 bytes, desc and origin with max_out entries, held
+        with one word per source frame, total as a REASS_TOTAL_FIELDS record."""
+        _, desc_dt = L.np_dtypes()
+        frames = np.ascontiguousarray(frames, dtype=np.uint8)
+        if desc is not None:
+            desc = np.ascontiguousarray(desc, dtype=desc_dt)
+        num = len(desc) if desc is not None else len(frames) // stride
+        uniform = isinstance(l3, (int, np.integer))
+        src = [frames, desc, None if uniform else np.ascontiguousarray(l3)]
+        fb, db, lb = (None if a is None else self.ctx.buffer(a.nbytes + 64) for a in src)
+        for b, a in zip((fb, db, lb), src):
+            if b:
+                b.upload(a)
+        sizes = (capacity + 64, 8 * max_out, 4 * max_out, num, 4 * num, 8, 24)
+        out = [self.ctx.buffer(n) for n in sizes]
+        for b in out:
+            L.check(lib.odpg_memset_dev(self.ctx.h, b.ptr, fill, b.nbytes), "memset")
+        self.run_dev(fb, num, out[0], capacity, out[1], max_out, *out[2:], stride=stride, desc_buf=db,
+                     l3_ptr=lb.ptr if lb else None, l3_stride=l3_stride,
+                     uniform_l3=int(l3) if uniform else 0)
+        self.ctx.sync()
+        res = (out[0].download(np.uint8, capacity + 64), out[1].download(desc_dt, max_out),
+               out[2].download(np.uint32, max_out), out[3].download(np.uint8, num),
+               out[4].download(np.uint32, num), out[5].download(np.uint32, 2),
+               out[6].download(np.dtype(L.REASS_TOTAL_FIELDS), 1)[0])
+        for b in (fb, db, lb, *out):
+            if b:
+                b.free()
+        return res
+
+    def close(self):
+        if self.h:
+            # valid after the context's destroy too (odpg.h "object lifetimes")
+            lib.odpg_reass_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        if sys.is_finalizing():   # the HIP runtime may be torn down already
+            return
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Context:
     def __init__(self, device=0, stream=None):
         n = lib.odpg_device_count()
@@ -388,6 +468,9 @@ class Context:
 
     def lso(self, profiles, max_pkts=1 << 16):
         return Lso(self, profiles, max_pkts)
+
+    def reass(self, max_pkts=1 << 16):
+        return Reass(self, max_pkts)
 
     def classify_dev(self, table, frames_buf, num, stride=0, desc_buf=None, opt=0,
                      layer=L.LAYER_ALL, classify=True, out_buf=None, mark_buf=None,
