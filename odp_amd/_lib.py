@@ -273,6 +273,29 @@ REASS_TOTAL_FIELDS = [("num_out", "<u4"), ("copied", "<u4"), ("num_held", "<u4")
                       ("num_bad", "<u4"), ("bytes", "<u8")]                    # 24 B
 
 
+# ---- include/odpg_switch.h --------------------------------------------------
+SWITCH_TILE = 256        # ODPG_SWITCH_TILE: packets one resolve / list workgroup handles
+SWITCH_UNICAST, SWITCH_FLOOD, SWITCH_DROP_FRAME, SWITCH_DROP_PORT = range(4)
+SWITCH_MAX_PORTS = 32
+SWITCH_TABLE_SIZE = 65536
+SWITCH_AGING_TIME = 5
+
+
+class odpg_switch_src_t(C.Structure):
+    _fields_ = [("frames", C.c_void_p), ("desc", C.c_void_p), ("stride", C.c_uint32),
+                ("num", C.c_uint32), ("port_in", C.c_void_p), ("uniform_port", C.c_uint8),
+                ("reserved", C.c_uint8 * 7)]
+
+
+class odpg_switch_dst_t(C.Structure):
+    _fields_ = [("out", C.c_void_p), ("lists", C.c_void_p), ("list_stride", C.c_uint32),
+                ("reserved", C.c_uint32), ("port_offsets", C.c_void_p), ("total", C.c_void_p)]
+
+
+SWITCH_TOTAL_FIELDS = [("unicast", "<u4"), ("flooded", "<u4"), ("dropped", "<u4"),
+                       ("entries", "<u4")]                                     # 16 B
+
+
 # ---- include/odpg_pcap.h ----------------------------------------------------
 class odpg_capture_t(C.Structure):
     _fields_ = [("frames", C.c_void_p), ("desc", C.c_void_p), ("num", C.c_uint32),
@@ -531,6 +554,12 @@ SIGNATURES = {
     "odpg_reass_create": (_i32, [_vp, _u32, C.POINTER(_vp)]),
     "odpg_reass_destroy": (None, [_vp]),
     "odpg_reass": (_i32, [_vp, C.POINTER(odpg_reass_src_t), C.POINTER(odpg_reass_dst_t)]),
+    # include/odpg_switch.h
+    "odpg_switch_create": (_i32, [_vp, _u32, _u32, C.POINTER(_vp)]),
+    "odpg_switch_destroy": (None, [_vp]),
+    "odpg_switch_table": (_vp, [_vp]),
+    "odpg_switch": (_i32, [_vp, C.POINTER(odpg_switch_src_t), C.c_uint8,
+                           C.POINTER(odpg_switch_dst_t)]),
     # include/odpg_group.h
     "odpg_group_create": (_i32, [C.POINTER(C.c_int), _u32, C.POINTER(_vp)]),
     "odpg_group_destroy": (None, [_vp]),

@@ -23,6 +23,7 @@
 #include "gather.h"
 #include "lso.h"
 #include "reass.h"
+#include "switch.h"
 #include "lanes.h"
 
 
@@ -1158,6 +1159,110 @@ int odpg_reass(odpg_reass_t *r, const odpg_reass_src_t *src, const odpg_reass_ds
 	std::lock_guard<std::mutex> lk(c->lock);
 
 	return odpg_launch_reass(&a, ctx_stream_locked(c));
+}
+
+/* ---- L2 switch (odpg_switch.h; kernels in switch.hip) ------------------------ */
+struct odpg_switch_s {
+	odpg_ctx_t *ctx;
+	uint32_t max_pkts;
+	odpg_switch_args a;            /* ports, table and device workspace */
+};
+
+static void switch_free(odpg_switch_t *w)
+{
+	odpg_ctx_t *c = w->ctx;
+
+	hipFree(w->a.table);
+	hipFree(w->a.rec);
+	hipFree(w->a.skey);
+	hipFree(w->a.mask);
+	hipFree(w->a.order);
+	hipFree(w->a.offsets);
+	hipFree(w->a.tcnt);
+	hipFree(w->a.hist);
+	hipFree(w->a.dtotal);
+	hipFree(w->a.bcount);
+	hipFree(w->a.pairs);
+	delete w;
+	odpg_ctx_unref(c);
+}
+
+int odpg_switch_create(odpg_ctx_t *c, uint32_t num_ports, uint32_t max_pkts, odpg_switch_t **out)
+{
+	/* a writer run's binary search and the tile counts rely on num <= 2^24 */
+	if (!c || !out || num_ports < 2u || num_ports > ODPG_SWITCH_MAX_PORTS ||
+	    max_pkts > (1u << 24))
+		return -EINVAL;
+	odpg_switch_t *w = new odpg_switch_t();
+	odpg_switch_args &a = w->a;
+	const size_t n = std::max<size_t>(max_pkts, 1u);
+	const size_t tiles = (n + SW_TILE - 1u) / SW_TILE;
+	const size_t hist_words = ((n + DLV_TILE - 1u) / DLV_TILE) << dlv_bits0(SW_KEY_BITS);
+	int rc = -ENOMEM;
+
+	w->ctx = c;
+	odpg_ctx_ref(c);
+	w->max_pkts = max_pkts;
+	a.num_ports = num_ports;
+	hipSetDevice(c->device);
+	if (hipMalloc(&a.table, (size_t)SW_SLOTS * 8u) == hipSuccess &&
+	    hipMalloc(&a.rec, n * sizeof(odpg_switch_rec)) == hipSuccess &&
+	    hipMalloc(&a.skey, n * 4u) == hipSuccess && hipMalloc(&a.mask, n * 4u) == hipSuccess &&
+	    hipMalloc(&a.order, n * 4u) == hipSuccess &&
+	    hipMalloc(&a.offsets, (size_t)(SW_BUCKETS + 1u) * 4u) == hipSuccess &&
+	    hipMalloc(&a.tcnt, tiles * SW_COLS * 4u) == hipSuccess &&
+	    hipMalloc(&a.hist, hist_words * 4u) == hipSuccess &&
+	    hipMalloc(&a.dtotal, DLV_RADIX * 4u) == hipSuccess &&
+	    hipMalloc(&a.bcount, (size_t)SW_BUCKETS * 4u) == hipSuccess &&
+	    hipMalloc(&a.pairs, n * 8u) == hipSuccess) {
+		std::lock_guard<std::mutex> g(c->lock);
+		hipStream_t cs = ctx_stream_locked(c);
+
+		/* on the context stream, like every later call and table copy */
+		rc = odpg_launch_switch_clear((uint32_t *)a.table, SW_SLOTS * 2u, cs) == 0 &&
+		     odpg_launch_switch_clear(a.dtotal, DLV_RADIX, cs) == 0 &&
+		     odpg_launch_switch_clear(a.bcount, SW_BUCKETS, cs) == 0 ? 0 : -EIO;
+	}
+	if (rc) {
+		switch_free(w);
+		return rc;
+	}
+	*out = w;
+	return 0;
+}
+
+void odpg_switch_destroy(odpg_switch_t *w)
+{
+	if (!w)
+		return;
+	hipSetDevice(w->ctx->device);
+	hipStreamSynchronize(ctx_stream(w->ctx));   /* launches still using the workspace */
+	switch_free(w);
+}
+
+uint64_t *odpg_switch_table(odpg_switch_t *w)
+{
+	return w ? w->a.table : nullptr;
+}
+
+int odpg_switch(odpg_switch_t *w, const odpg_switch_src_t *src, uint8_t cur_tick,
+		const odpg_switch_dst_t *dst)
+{
+	if (!w || !src || !dst || !dst->out || !dst->lists || !dst->port_offsets || !dst->total ||
+	    (!src->frames && src->num) || ((uintptr_t)src->frames & 15u) ||
+	    (!src->desc && (!src->stride || (src->stride & 15u))) || src->num > w->max_pkts ||
+	    dst->list_stride < src->num)
+		return -EINVAL;
+	odpg_ctx_t *c = w->ctx;
+	odpg_switch_args a = w->a;
+
+	a.src = *src;
+	a.dst = *dst;
+	a.cur_tick = cur_tick;
+	hipSetDevice(c->device);
+	std::lock_guard<std::mutex> lk(c->lock);
+
+	return odpg_launch_switch(&a, ctx_stream_locked(c));
 }
 
 static int ensure_ws(odpg_ctx_t *c, size_t bytes)

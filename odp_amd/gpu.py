@@ -421,6 +421,93 @@ class Reass:
             pass
 
 
+class Switch:
+    """L2 learning switch (include/odpg_switch.h): a batch's frames looked up
+    in and taught to a MAC table on the device, in index order, with a list
+    of frame indices per egress port."""
+
+    def __init__(self, ctx, num_ports, max_pkts):
+        h = C.c_void_p()
+        L.check(lib.odpg_switch_create(ctx.h, num_ports, max_pkts, C.byref(h)),
+                "odpg_switch_create")
+        self.h = h.value
+        self.ctx = ctx
+        self.num_ports = num_ports
+        self.max_pkts = max_pkts
+        self.table_ptr = lib.odpg_switch_table(self.h)
+
+    def table(self):
+        """The MAC table as 65536 u64 entries (bytes 0-5 MAC, 6 port, 7 tick)."""
+        t = np.empty(L.SWITCH_TABLE_SIZE, "<u8")
+        L.check(lib.odpg_memcpy_d2h(self.ctx.h, t.ctypes.data, self.table_ptr, t.nbytes), "d2h")
+        return t
+
+    def set_table(self, entries):
+        t = np.ascontiguousarray(entries, dtype="<u8")
+        assert len(t) == L.SWITCH_TABLE_SIZE
+        L.check(lib.odpg_memcpy_h2d(self.ctx.h, self.table_ptr, t.ctypes.data, t.nbytes), "h2d")
+
+    def run_dev(self, frames_buf, num, cur_tick, out_buf, lists_buf, list_stride,
+                port_offsets_buf, total_buf, stride=0, desc_buf=None, port_in_buf=None,
+                uniform_port=0):
+        """Asynchronous on the context stream: out_buf (num words), lists_buf
+        (num_ports x list_stride words), port_offsets_buf (2 x num_ports
+        words), total_buf (odpg_switch_total_t). port_in_buf holds a byte per
+        packet; without it uniform_port applies to every packet."""
+        s = L.odpg_switch_src_t(frames_buf.ptr, desc_buf.ptr if desc_buf else None, stride, num,
+                                port_in_buf.ptr if port_in_buf else None, uniform_port)
+        d = L.odpg_switch_dst_t(out_buf.ptr, lists_buf.ptr, list_stride, 0,
+                                port_offsets_buf.ptr, total_buf.ptr)
+        L.check(lib.odpg_switch(self.h, C.byref(s), cur_tick, C.byref(d)), "odpg_switch")
+
+    def run(self, frames, port_in, cur_tick, stride=0, desc=None, list_stride=None, fill=0):
+        """Upload, switch, download (out, lists[num_ports, list_stride],
+        port_offsets, total). `port_in` is an int (one ingress port for all)
+        or a byte per packet. The batch has len(desc) frames, or
+        len(frames) // stride. Every destination buffer is set to the byte
+        `fill` first; total is a SWITCH_TOTAL_FIELDS record."""
+        _, desc_dt = L.np_dtypes()
+        frames = np.ascontiguousarray(frames, dtype=np.uint8)
+        if desc is not None:
+            desc = np.ascontiguousarray(desc, dtype=desc_dt)
+        num = len(desc) if desc is not None else len(frames) // stride
+        ls = num if list_stride is None else list_stride
+        uniform = isinstance(port_in, (int, np.integer))
+        src = [frames, desc, None if uniform else np.ascontiguousarray(port_in, dtype=np.uint8)]
+        fb, db, pb = (None if a is None else self.ctx.buffer(a.nbytes + 64) for a in src)
+        for b, a in zip((fb, db, pb), src):
+            if b:
+                b.upload(a)
+        P = self.num_ports
+        out = [self.ctx.buffer(n) for n in (4 * num, 4 * P * ls, 8 * P, 16)]
+        for b in out:
+            L.check(lib.odpg_memset_dev(self.ctx.h, b.ptr, fill, b.nbytes), "memset")
+        self.run_dev(fb, num, cur_tick, out[0], out[1], ls, out[2], out[3], stride=stride,
+                     desc_buf=db, port_in_buf=pb, uniform_port=int(port_in) if uniform else 0)
+        self.ctx.sync()
+        res = (out[0].download(np.uint32, num), out[1].download(np.uint32, P * ls).reshape(P, ls),
+               out[2].download(np.uint32, 2 * P),
+               out[3].download(np.dtype(L.SWITCH_TOTAL_FIELDS), 1)[0])
+        for b in (fb, db, pb, *out):
+            if b:
+                b.free()
+        return res
+
+    def close(self):
+        if self.h:
+            # valid after the context's destroy too (odpg.h "object lifetimes")
+            lib.odpg_switch_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        if sys.is_finalizing():   # the HIP runtime may be torn down already
+            return
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Context:
     def __init__(self, device=0, stream=None):
         n = lib.odpg_device_count()
@@ -471,6 +558,9 @@ class Context:
 
     def reass(self, max_pkts=1 << 16):
         return Reass(self, max_pkts)
+
+    def switch(self, num_ports, max_pkts=1 << 20):
+        return Switch(self, num_ports, max_pkts)
 
     def classify_dev(self, table, frames_buf, num, stride=0, desc_buf=None, opt=0,
                      layer=L.LAYER_ALL, classify=True, out_buf=None, mark_buf=None,
