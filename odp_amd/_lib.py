@@ -296,6 +296,49 @@ SWITCH_TOTAL_FIELDS = [("unicast", "<u4"), ("flooded", "<u4"), ("dropped", "<u4"
                        ("entries", "<u4")]                                     # 16 B
 
 
+# ---- include/odpg_esp.h -----------------------------------------------------
+ESP_TILE = 16            # ODPG_ESP_TILE: packets one crypt workgroup handles
+ESP_MAX_SAS = 2048
+ESP_OUT, ESP_IN = 0, 1
+(ESP_OK, ESP_NO_SA, ESP_BAD_L3, ESP_MTU, ESP_BAD_PROTO, ESP_BAD_SPI, ESP_BAD_LEN, ESP_AUTH,
+ ESP_BAD_PAD, ESP_BAD_NEXT) = range(10)
+
+
+class odpg_esp_sa_t(C.Structure):
+    _fields_ = [("spi", C.c_uint32), ("key", C.c_uint8 * 32), ("key_len", C.c_uint32),
+                ("salt", C.c_uint8 * 4), ("tun_src", C.c_uint8 * 4), ("tun_dst", C.c_uint8 * 4),
+                ("ttl", C.c_uint8), ("dscp", C.c_uint8), ("df", C.c_uint8),
+                ("copy_dscp", C.c_uint8), ("copy_df", C.c_uint8), ("reserved", C.c_uint8),
+                ("mtu", C.c_uint16)]
+
+
+class odpg_esp_src_t(C.Structure):
+    _fields_ = [("frames", C.c_void_p), ("desc", C.c_void_p), ("stride", C.c_uint32),
+                ("num", C.c_uint32), ("sa", C.c_void_p), ("l3_offset", C.c_void_p),
+                ("uniform_sa", C.c_uint16), ("uniform_l3", C.c_uint16), ("reserved", C.c_uint32)]
+
+
+class odpg_esp_dst_t(C.Structure):
+    _fields_ = [("frames", C.c_void_p), ("capacity", C.c_uint64), ("desc", C.c_void_p),
+                ("max_out", C.c_uint32), ("reserved", C.c_uint32), ("status", C.c_void_p),
+                ("seq", C.c_void_p), ("total", C.c_void_p)]
+
+
+ESP_TOTAL_FIELDS = [("num_out", "<u4"), ("copied", "<u4"), ("first_bad", "<u4"),
+                    ("reserved", "<u4"), ("bytes", "<u8")]                     # 24 B
+
+
+def esp_sa(spi, key, salt, tun_src=bytes(4), tun_dst=bytes(4), ttl=64, dscp=0, df=0,
+           copy_dscp=0, copy_df=0, mtu=0xFFFF):
+    """odpg_esp_sa_t from bytes objects and integers."""
+    sa = odpg_esp_sa_t(spi=spi, key_len=len(key), ttl=ttl, dscp=dscp, df=df,
+                       copy_dscp=copy_dscp, copy_df=copy_df, mtu=mtu)
+    C.memmove(sa.key, bytes(key), min(len(key), 32))
+    for name, v in (("salt", salt), ("tun_src", tun_src), ("tun_dst", tun_dst)):
+        C.memmove(getattr(sa, name), bytes(v), 4)
+    return sa
+
+
 # ---- include/odpg_pcap.h ----------------------------------------------------
 class odpg_capture_t(C.Structure):
     _fields_ = [("frames", C.c_void_p), ("desc", C.c_void_p), ("num", C.c_uint32),
@@ -560,6 +603,13 @@ SIGNATURES = {
     "odpg_switch_table": (_vp, [_vp]),
     "odpg_switch": (_i32, [_vp, C.POINTER(odpg_switch_src_t), C.c_uint8,
                            C.POINTER(odpg_switch_dst_t)]),
+    # include/odpg_esp.h
+    "odpg_esp_key_schedule": (_i32, [_vp, _u32, _vp, _vp]),
+    "odpg_esp_create": (_i32, [_vp, _u32, _u32, _u32, C.POINTER(_vp)]),
+    "odpg_esp_destroy": (None, [_vp]),
+    "odpg_esp_sa_set": (_i32, [_vp, _u32, C.POINTER(odpg_esp_sa_t)]),
+    "odpg_esp_next_seq": (_vp, [_vp]),
+    "odpg_esp": (_i32, [_vp, C.POINTER(odpg_esp_src_t), C.POINTER(odpg_esp_dst_t)]),
     # include/odpg_group.h
     "odpg_group_create": (_i32, [C.POINTER(C.c_int), _u32, C.POINTER(_vp)]),
     "odpg_group_destroy": (None, [_vp]),

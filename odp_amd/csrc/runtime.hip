@@ -24,6 +24,7 @@
 #include "lso.h"
 #include "reass.h"
 #include "switch.h"
+#include "esp.h"
 #include "lanes.h"
 
 
@@ -1263,6 +1264,239 @@ int odpg_switch(odpg_switch_t *w, const odpg_switch_src_t *src, uint8_t cur_tick
 	std::lock_guard<std::mutex> lk(c->lock);
 
 	return odpg_launch_switch(&a, ctx_stream_locked(c));
+}
+
+/* ---- ESP tunnel AES-GCM (odpg_esp.h; kernels in esp.hip) ---------------------- */
+struct odpg_esp_s {
+	odpg_ctx_t *ctx;
+	uint32_t max_pkts;
+	odpg_esp_sa_dev *sas;          /* device */
+	uint32_t *te0;                 /* device */
+	odpg_esp_args a;               /* direction, SAs and device workspace */
+};
+
+/* S-box by the walk over the powers of the generator 3 and their inverses,
+ * then te0[x] = {02, 01, 01, 03} . S[x] (esp.h) */
+static const uint32_t *esp_te0()
+{
+	static uint32_t te0[256];
+	static std::once_flag once;
+
+	std::call_once(once, [] {
+		uint8_t sbox[256], p = 1, q = 1;
+
+		do {
+			p = (uint8_t)(p ^ (p << 1) ^ ((p & 0x80u) ? 0x1Bu : 0u));
+			q ^= (uint8_t)(q << 1);
+			q ^= (uint8_t)(q << 2);
+			q ^= (uint8_t)(q << 4);
+			q ^= (q & 0x80u) ? 0x09u : 0u;
+			const uint8_t x = (uint8_t)(q ^ (q << 1 | q >> 7) ^ (q << 2 | q >> 6) ^
+						    (q << 3 | q >> 5) ^ (q << 4 | q >> 4));
+			sbox[p] = x ^ 0x63u;
+		} while (p != 1);
+		sbox[0] = 0x63u;
+		for (uint32_t i = 0; i < 256u; i++) {
+			const uint32_t s = sbox[i], s2 = ((s << 1) ^ ((s & 0x80u) ? 0x11Bu : 0u)) & 0xFFu;
+
+			te0[i] = s2 << 24 | s << 16 | s << 8 | (s2 ^ s);
+		}
+	});
+	return te0;
+}
+
+int odpg_esp_key_schedule(const uint8_t *key, uint32_t key_len, uint32_t rk[60], uint8_t h[16])
+{
+	if (!key || !rk || !h || (key_len != 16u && key_len != 24u && key_len != 32u))
+		return -EINVAL;
+	const uint32_t *te0 = esp_te0();
+	const uint32_t nk = key_len / 4u, nr = nk + 6u, words = 4u * (nr + 1u);
+	uint32_t rcon = 1, z[4] = {0u, 0u, 0u, 0u};
+	auto sub = [te0](uint32_t w) {
+		return ((te0[w >> 24] >> 8) & 0xFFu) << 24 | ((te0[(w >> 16) & 0xFFu] >> 8) & 0xFFu) << 16 |
+		       ((te0[(w >> 8) & 0xFFu] >> 8) & 0xFFu) << 8 | ((te0[w & 0xFFu] >> 8) & 0xFFu);
+	};
+
+	memset(rk, 0, 60u * sizeof(uint32_t));
+	for (uint32_t i = 0; i < nk; i++)
+		rk[i] = (uint32_t)key[4 * i] << 24 | (uint32_t)key[4 * i + 1] << 16 |
+			(uint32_t)key[4 * i + 2] << 8 | key[4 * i + 3];
+	for (uint32_t i = nk; i < words; i++) {
+		uint32_t t = rk[i - 1];
+
+		if (i % nk == 0) {
+			t = sub(t << 8 | t >> 24) ^ rcon << 24;
+			rcon = ((rcon << 1) ^ ((rcon & 0x80u) ? 0x11Bu : 0u)) & 0xFFu;
+		} else if (nk > 6u && i % nk == 4u) {
+			t = sub(t);
+		}
+		rk[i] = rk[i - nk] ^ t;
+	}
+	esp_aes_encrypt(rk, nr, te0, z);
+	for (uint32_t i = 0; i < 16u; i++)
+		h[i] = (uint8_t)(z[i >> 2] >> (24u - 8u * (i & 3u)));
+	return 0;
+}
+
+static void esp_free(odpg_esp_t *e)
+{
+	odpg_ctx_t *c = e->ctx;
+	odpg_esp_args &a = e->a;
+
+	hipFree(e->sas);
+	hipFree(e->te0);
+	hipFree(a.next_seq);
+	hipFree(a.rec);
+	hipFree(a.ounit);
+	hipFree(a.seq64);
+	hipFree(a.tunits);
+	hipFree(a.tok);
+	hipFree(a.tbad);
+	hipFree(a.skey);
+	hipFree(a.order);
+	hipFree(a.offsets);
+	hipFree(a.hist);
+	hipFree(a.dtotal);
+	hipFree(a.bcount);
+	hipFree(a.pairs);
+	delete e;
+	odpg_ctx_unref(c);
+}
+
+int odpg_esp_create(odpg_ctx_t *c, uint32_t dir, uint32_t max_sas, uint32_t max_pkts,
+		    odpg_esp_t **out)
+{
+	if (!c || !out || (dir != ODPG_ESP_OUT && dir != ODPG_ESP_IN) || !max_sas ||
+	    max_sas > ODPG_ESP_MAX_SAS || max_pkts > (1u << 24))
+		return -EINVAL;
+	odpg_esp_t *e = new odpg_esp_t();
+	odpg_esp_args &a = e->a;
+	const size_t n = std::max<size_t>(max_pkts, 1u);
+	const size_t tiles = (n + ESP_PREP_WG - 1u) / ESP_PREP_WG;
+	const bool is_out = dir == ODPG_ESP_OUT;
+	const size_t sa_words = (size_t)max_sas * sizeof(odpg_esp_sa_dev) / 4u;
+	int rc = -ENOMEM;
+
+	e->ctx = c;
+	odpg_ctx_ref(c);
+	e->max_pkts = max_pkts;
+	a.dir = dir;
+	a.max_sas = max_sas;
+	a.key_bits = dlv_key_bits(max_sas + 1u);
+	const size_t hist_words = ((n + DLV_TILE - 1u) / DLV_TILE) << dlv_bits0(a.key_bits);
+	const bool two = a.key_bits > DLV_DIGIT_BITS;
+
+	hipSetDevice(c->device);
+	if (hipMalloc(&e->sas, sa_words * 4u) == hipSuccess &&
+	    hipMalloc(&e->te0, 1024u) == hipSuccess &&
+	    hipMalloc(&a.rec, n * sizeof(odpg_esp_rec)) == hipSuccess &&
+	    hipMalloc(&a.ounit, n * 4u) == hipSuccess &&
+	    hipMalloc(&a.tunits, tiles * 8u) == hipSuccess &&
+	    hipMalloc(&a.tok, tiles * 4u) == hipSuccess && hipMalloc(&a.tbad, tiles * 4u) == hipSuccess &&
+	    (!is_out ||
+	     (hipMalloc(&a.next_seq, (size_t)max_sas * 8u) == hipSuccess &&
+	      hipMalloc(&a.seq64, n * 8u) == hipSuccess && hipMalloc(&a.skey, n * 4u) == hipSuccess &&
+	      hipMalloc(&a.order, n * 4u) == hipSuccess &&
+	      hipMalloc(&a.offsets, (size_t)(max_sas + 2u) * 4u) == hipSuccess &&
+	      hipMalloc(&a.hist, hist_words * 4u) == hipSuccess &&
+	      hipMalloc(&a.dtotal, DLV_RADIX * 4u) == hipSuccess &&
+	      (!two || (hipMalloc(&a.bcount, (size_t)(max_sas + 1u) * 4u) == hipSuccess &&
+			hipMalloc(&a.pairs, n * 8u) == hipSuccess))))) {
+		std::lock_guard<std::mutex> g(c->lock);
+		hipStream_t cs = ctx_stream_locked(c);
+
+		/* on the context stream, like every later call and SA upload */
+		rc = hipMemcpyAsync(e->te0, esp_te0(), 1024u, hipMemcpyHostToDevice, cs) == hipSuccess &&
+		     odpg_launch_esp_clear((uint32_t *)e->sas, (uint32_t)sa_words, cs) == 0 &&
+		     (!is_out ||
+		      (odpg_launch_esp_clear((uint32_t *)a.next_seq, max_sas * 2u, cs) == 0 &&
+		       odpg_launch_esp_clear(a.dtotal, DLV_RADIX, cs) == 0 &&
+		       (!two || odpg_launch_esp_clear(a.bcount, max_sas + 1u, cs) == 0))) ? 0 : -EIO;
+	}
+	if (rc) {
+		esp_free(e);
+		return rc;
+	}
+	a.sas = e->sas;
+	a.te0 = e->te0;
+	*out = e;
+	return 0;
+}
+
+void odpg_esp_destroy(odpg_esp_t *e)
+{
+	if (!e)
+		return;
+	hipSetDevice(e->ctx->device);
+	hipStreamSynchronize(ctx_stream(e->ctx));   /* launches still using the workspace */
+	esp_free(e);
+}
+
+uint64_t *odpg_esp_next_seq(odpg_esp_t *e)
+{
+	return e ? e->a.next_seq : nullptr;
+}
+
+int odpg_esp_sa_set(odpg_esp_t *e, uint32_t index, const odpg_esp_sa_t *sa)
+{
+	if (!e || index >= e->a.max_sas)
+		return -EINVAL;
+	odpg_esp_sa_dev d;
+	const uint64_t one = 1;
+
+	memset(&d, 0, sizeof(d));
+	if (sa) {
+		uint8_t h[16];
+
+		if (odpg_esp_key_schedule(sa->key, sa->key_len, d.rk, h))
+			return -EINVAL;
+		for (uint32_t w = 0; w < 4u; w++)
+			d.hpow[0][w] = (uint32_t)h[4 * w] << 24 | (uint32_t)h[4 * w + 1] << 16 |
+				       (uint32_t)h[4 * w + 2] << 8 | h[4 * w + 3];
+		for (uint32_t k = 1; k < ESP_NPOW; k++)
+			esp_gf_mul(d.hpow[k - 1u], d.hpow[0], d.hpow[k]);
+		d.nr = sa->key_len / 4u + 6u;
+		d.salt = (uint32_t)sa->salt[0] << 24 | (uint32_t)sa->salt[1] << 16 |
+			 (uint32_t)sa->salt[2] << 8 | sa->salt[3];
+		d.spi = sa->spi;
+		d.flags = ESP_SA_VALID | (sa->df ? ESP_SA_DF : 0u) |
+			  (sa->copy_dscp ? ESP_SA_COPY_DSCP : 0u) | (sa->copy_df ? ESP_SA_COPY_DF : 0u);
+		d.tun_src = (uint32_t)sa->tun_src[0] << 24 | (uint32_t)sa->tun_src[1] << 16 |
+			    (uint32_t)sa->tun_src[2] << 8 | sa->tun_src[3];
+		d.tun_dst = (uint32_t)sa->tun_dst[0] << 24 | (uint32_t)sa->tun_dst[1] << 16 |
+			    (uint32_t)sa->tun_dst[2] << 8 | sa->tun_dst[3];
+		d.ttl_dscp = sa->ttl | (uint32_t)(sa->dscp & 0x3Fu) << 8;
+		d.mtu = sa->mtu;
+	}
+	odpg_ctx_t *c = e->ctx;
+
+	hipSetDevice(c->device);
+	/* synchronous on the context stream: after the calls before it, before the
+	 * calls after it */
+	if (odpg_memcpy_h2d(c, e->sas + index, &d, sizeof(d)))
+		return -EIO;
+	if (e->a.next_seq && odpg_memcpy_h2d(c, e->a.next_seq + index, &one, sizeof(one)))
+		return -EIO;
+	return 0;
+}
+
+int odpg_esp(odpg_esp_t *e, const odpg_esp_src_t *src, const odpg_esp_dst_t *dst)
+{
+	if (!e || !src || !dst || !dst->frames || !dst->status || !dst->seq || !dst->total ||
+	    (!dst->desc && dst->max_out) || (!src->frames && src->num) ||
+	    (((uintptr_t)src->frames | (uintptr_t)dst->frames) & 15u) ||
+	    (((uintptr_t)src->sa | (uintptr_t)src->l3_offset) & 1u) || src->num > e->max_pkts ||
+	    (!src->desc && (!src->stride || (src->stride & 15u))) || dst->capacity > (1ull << 32))
+		return -EINVAL;
+	odpg_ctx_t *c = e->ctx;
+	odpg_esp_args a = e->a;
+
+	a.src = *src;
+	a.dst = *dst;
+	hipSetDevice(c->device);
+	std::lock_guard<std::mutex> lk(c->lock);
+
+	return odpg_launch_esp(&a, ctx_stream_locked(c));
 }
 
 static int ensure_ws(odpg_ctx_t *c, size_t bytes)

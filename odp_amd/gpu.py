@@ -508,6 +508,101 @@ class Switch:
             pass
 
 
+class Esp:
+    """ESP plan (include/odpg_esp.h): the frames of a batch encapsulated and
+    encrypted (ESP_OUT) or authenticated, decrypted and decapsulated (ESP_IN)
+    on the device, tunnel mode over IPv4 with AES-GCM."""
+
+    def __init__(self, ctx, direction, max_sas, max_pkts):
+        h = C.c_void_p()
+        L.check(lib.odpg_esp_create(ctx.h, direction, max_sas, max_pkts, C.byref(h)),
+                "odpg_esp_create")
+        self.h = h.value
+        self.ctx = ctx
+        self.dir = direction
+        self.max_sas = max_sas
+        self.max_pkts = max_pkts
+        self.next_seq_ptr = lib.odpg_esp_next_seq(self.h)
+
+    def set_sa(self, index, sa):
+        """sa: an odpg_esp_sa_t (L.esp_sa builds one), or None to clear the SA."""
+        L.check(lib.odpg_esp_sa_set(self.h, index, C.byref(sa) if sa is not None else None),
+                "odpg_esp_sa_set")
+
+    def next_seq(self):
+        """The outbound sequence counters, one u64 per SA."""
+        t = np.empty(self.max_sas, "<u8")
+        L.check(lib.odpg_memcpy_d2h(self.ctx.h, t.ctypes.data, self.next_seq_ptr, t.nbytes), "d2h")
+        return t
+
+    def set_next_seq(self, values):
+        t = np.ascontiguousarray(values, dtype="<u8")
+        assert len(t) == self.max_sas
+        L.check(lib.odpg_memcpy_h2d(self.ctx.h, self.next_seq_ptr, t.ctypes.data, t.nbytes), "h2d")
+
+    def run_dev(self, frames_buf, num, dst_buf, capacity, dst_desc_buf, max_out, status_buf,
+                seq_buf, total_buf, stride=0, desc_buf=None, sa_buf=None, uniform_sa=0,
+                l3_buf=None, uniform_l3=14):
+        """Asynchronous on the context stream: the output frames into dst_buf
+        (capacity bytes), dst_desc_buf (max_out entries), status_buf (num
+        bytes), seq_buf (num words), total_buf (odpg_esp_total_t). sa_buf and
+        l3_buf hold a u16 per packet; without them uniform_sa / uniform_l3
+        apply to every packet."""
+        s = L.odpg_esp_src_t(frames_buf.ptr, desc_buf.ptr if desc_buf else None, stride, num,
+                             sa_buf.ptr if sa_buf else None, l3_buf.ptr if l3_buf else None,
+                             uniform_sa, uniform_l3, 0)
+        d = L.odpg_esp_dst_t(dst_buf.ptr, capacity, dst_desc_buf.ptr, max_out, 0, status_buf.ptr,
+                             seq_buf.ptr, total_buf.ptr)
+        L.check(lib.odpg_esp(self.h, C.byref(s), C.byref(d)), "odpg_esp")
+
+    def run(self, frames, sa, l3, stride=0, desc=None, capacity=0, max_out=0, fill=0):
+        """Upload, run, download (frames, desc, status, seq, total). `sa` and
+        `l3` are an int (one for all) or a u16 per packet. The batch has
+        len(desc) frames, or len(frames) // stride. Every destination buffer
+        is set to the byte `fill` first; frames come back as capacity + 64
+        bytes, desc with max_out entries, total as an ESP_TOTAL_FIELDS record."""
+        _, desc_dt = L.np_dtypes()
+        frames = np.ascontiguousarray(frames, dtype=np.uint8)
+        if desc is not None:
+            desc = np.ascontiguousarray(desc, dtype=desc_dt)
+        num = len(desc) if desc is not None else len(frames) // stride
+        usa, ul3 = (isinstance(v, (int, np.integer)) for v in (sa, l3))
+        src = [frames, desc, None if usa else np.ascontiguousarray(sa, dtype="<u2"),
+               None if ul3 else np.ascontiguousarray(l3, dtype="<u2")]
+        fb, db, sb, lb = (None if a is None else self.ctx.buffer(a.nbytes + 64) for a in src)
+        for b, a in zip((fb, db, sb, lb), src):
+            if b:
+                b.upload(a)
+        out = [self.ctx.buffer(n) for n in (capacity + 64, 8 * max_out, num, 4 * num, 24)]
+        for b in out:
+            L.check(lib.odpg_memset_dev(self.ctx.h, b.ptr, fill, b.nbytes), "memset")
+        self.run_dev(fb, num, out[0], capacity, out[1], max_out, out[2], out[3], out[4],
+                     stride=stride, desc_buf=db, sa_buf=sb, uniform_sa=int(sa) if usa else 0,
+                     l3_buf=lb, uniform_l3=int(l3) if ul3 else 0)
+        self.ctx.sync()
+        res = (out[0].download(np.uint8, capacity + 64), out[1].download(desc_dt, max_out),
+               out[2].download(np.uint8, num), out[3].download(np.uint32, num),
+               out[4].download(np.dtype(L.ESP_TOTAL_FIELDS), 1)[0])
+        for b in (fb, db, sb, lb, *out):
+            if b:
+                b.free()
+        return res
+
+    def close(self):
+        if self.h:
+            # valid after the context's destroy too (odpg.h "object lifetimes")
+            lib.odpg_esp_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        if sys.is_finalizing():   # the HIP runtime may be torn down already
+            return
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Context:
     def __init__(self, device=0, stream=None):
         n = lib.odpg_device_count()
@@ -561,6 +656,9 @@ class Context:
 
     def switch(self, num_ports, max_pkts=1 << 20):
         return Switch(self, num_ports, max_pkts)
+
+    def esp(self, direction, max_sas, max_pkts=1 << 20):
+        return Esp(self, direction, max_sas, max_pkts)
 
     def classify_dev(self, table, frames_buf, num, stride=0, desc_buf=None, opt=0,
                      layer=L.LAYER_ALL, classify=True, out_buf=None, mark_buf=None,
