@@ -209,7 +209,12 @@ typedef struct odpg_result_s {
  * 1697-1698, odp_classification_internal.h:64-78) accumulate in a device
  * block with one row per workgroup of the resident grid: each workgroup adds
  * its counts into its own row at its end (no atomics between workgroups, no
- * extra kernel per launch). odpg_counters_fold() sums the rows, adds the
+ * extra kernel per launch). On a context with two launch lanes (below) the
+ * block holds one such set of rows per lane and a launch adds into the set of
+ * the lane it runs on, so counted launches on both lanes share no row; where
+ * two sets would exceed the block's size limit the object keeps one and its
+ * launches stay in order on the context stream. odpg_counters_fold() sums the
+ * rows of every set, adds the
  * totals to the caller's words and clears the rows, ordered on the context
  * stream after every launch enqueued before it; the reference reads its
  * counters the same way, at query time (odp_cls_cos_stats, odp_pktio_stats).
@@ -241,18 +246,22 @@ int         odpg_device_count(void);
  * its device only. */
 int  odpg_ctx_create(int device, void *stream, odpg_ctx_t **ctx);
 void odpg_ctx_destroy(odpg_ctx_t *ctx);
-/* Launch lanes. A context that created its own stream runs verdict-only
- * odpg_classify launches (res->stats and res->counters NULL) on two streams,
- * alternately, so that one launch's workgroups fill the compute units the
- * previous launch's last waves leave. The contract does not change:
+/* Launch lanes. A context that created its own stream runs odpg_classify
+ * launches without a caller's stats block (res->stats NULL: verdict-only, or
+ * counted into a counters object with a set of rows per lane, "sharded
+ * counters" above) on two streams, alternately, so that one launch's
+ * workgroups fill the compute units the previous launch's last waves leave.
+ * The contract does not change:
  *   - results are as if the launches ran in call order: a launch that reads
  *     or writes bytes an earlier launch writes, or writes bytes it reads,
  *     runs after it (the library tracks the frame / descriptor / out / mark /
  *     meta ranges of the launches in flight);
- *   - every other call on the context (counted and stats launches, copies,
- *     fences, events, odpg_ctx_sync, table updates, odpg_deliver / gather /
- *     lso / reass / l3fwd / tx_prepare, ...) is ordered after all earlier launches,
- *     and later launches after it.
+ *   - every other call on the context (stats launches, odpg_classify_host,
+ *     odpg_counters_fold, copies, fences, events, odpg_ctx_sync, table
+ *     updates, odpg_deliver / gather / lso / reass / l3fwd / tx_prepare, ...)
+ *     is ordered after all earlier launches, and later launches after it; the
+ *     first launch after such a call runs on the context stream, so a caller
+ *     that alternates launch and read-back pays nothing for the second lane.
  * odpg_ctx_lanes() is 2 for such a context and 1 for a context on a caller's
  * stream. odpg_ctx_stream() hands the raw context stream out: the caller may
  * then enqueue work the library cannot see, so the context joins its lanes
@@ -306,8 +315,8 @@ int  odpg_counters_match(const odpg_counters_t *cnt, const odpg_table_t *tbl);
 int  odpg_counters_fold(odpg_counters_t *cnt, uint64_t *words);
 
 /* Device-resident batch: frames/desc/results all in HBM. Asynchronous, in
- * call order on the context ("launch lanes" above: a verdict-only launch may
- * overlap the previous one where they touch different memory). */
+ * call order on the context ("launch lanes" above: a verdict-only or counted
+ * launch may overlap the previous one where they touch different memory). */
 int odpg_classify(odpg_ctx_t *ctx, const odpg_table_t *tbl,
 		  const odpg_batch_t *batch, const odpg_result_t *res);
 

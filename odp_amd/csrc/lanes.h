@@ -1,10 +1,11 @@
 /* SPDX-License-Identifier: BSD-3-Clause
  *
- * Launch lanes: the bookkeeping that lets consecutive verdict-only
- * odpg_classify launches of one context run on two streams ("lanes") while
- * results stay what call order gives. Plain C without HIP: runtime.hip
- * carries out the actions decided here with HIP events, tests/c/lanes_model.cpp
- * carries them out in a happens-before model.
+ * Launch lanes: the bookkeeping that lets consecutive odpg_classify launches
+ * of one context (verdict-only, or counted into per-lane counter rows) run on
+ * two streams ("lanes") while results stay what call order gives. Plain C
+ * without HIP: runtime.hip carries out the actions decided here with HIP
+ * events, tests/c/lanes_model.cpp and lanes_join_model.cpp carry them out in
+ * a happens-before model.
  *
  * Lane 0 is the context stream, lane 1 the second stream. Each lane keeps a
  * bounded ring of the byte ranges read and written by those of its launches
@@ -26,7 +27,45 @@
  *
  * Every other use of the context stream is a join (lane_join): lane 0 waits
  * for lane 1's recorded launches, and the next launch on lane 1 first waits
- * for lane 0 (`dirty`).
+ * for lane 0 (`dirty`). A join leaves lane 0 as the next lane, so a caller
+ * that alternates launch and join stays on lane 0 and never records an
+ * event; while `dirty` is set lane 0's ring is only a hint for the choice of
+ * lane (lane 1 waits for all of lane 0 anyway) and drops its oldest entry
+ * when full. Lane 1 has to wait for a point of lane 0 behind the join's work
+ * and, to stay unordered with the launch that follows the join, in front of
+ * that launch. No event can be recorded there after the fact, so when the
+ * join itself had to wait for lane 1 (the caller does overlap launches:
+ * `fork`) the first launch after it records lane 0's event in front of
+ * itself; otherwise the event is recorded when lane 1 is first used, behind
+ * the launches lane 0 has taken since.
+ *
+ * The join state (`dirty`, `fork`, `join_epoch`) and what moves it:
+ *
+ *   call                         | before          | actions decided           | after
+ *   -----------------------------+-----------------+---------------------------+----------------
+ *   lane_join, lane 1 ring empty | any             | none                      | dirty 1
+ *   lane_join, lane 1 ring used  | any             | lane 0 waits for lane 1   | dirty 1, fork 1
+ *   launch on lane 0             | dirty 1, fork 1 | record E on lane 0        | dirty 2, fork 0,
+ *                                |                 |                           | join_epoch = E
+ *   launch on lane 0             | otherwise       | none for the join         | fork 0
+ *   launch on lane 1             | dirty 1         | record on lane 0, lane 1  | dirty 0, lane 0
+ *                                |                 | waits for it              | ring emptied
+ *   launch on lane 1             | dirty 2         | lane 1 waits for E        | dirty 0, lane 0
+ *                                |                 |                           | ring cut up to E
+ *   launch on lane 1             | dirty 0         | none for the join         | unchanged
+ *
+ * Invariants: dirty != 0 exactly when lane 0 holds work (a join's, or
+ * launches before it) lane 1 is not ordered after; dirty == 2 implies that
+ * event join_epoch of lane 0 was recorded behind the last join and in front
+ * of every lane-0 launch since (a later record into the same slot is a later
+ * point of the same stream, so waiting for the slot still orders after E);
+ * fork is set by a join and cleared by the first two-lane launch after it,
+ * which is always on lane 0 (lane 1's ring is empty after a join and `next`
+ * is 0; with one lane lane_launch decides nothing and leaves it). While
+ * dirty == 1 every record of lane 0's ring, and while dirty == 2 those of
+ * epochs up to join_epoch, are covered by the wait lane 1 does before its next
+ * launch, so a full ring may drop them without an event. lane_set is a join
+ * that also empties lane 0's ring.
  */
 #ifndef ODPG_LANES_H_
 #define ODPG_LANES_H_
@@ -68,7 +107,10 @@ typedef struct lane_state {
 	lane_ring r[2];
 	int lanes;           /* 2: eligible launches alternate; 1: all on lane 0 */
 	int next;            /* lane of the next eligible launch */
-	int dirty;           /* lane 0 has work lane 1 is not ordered after */
+	int dirty;           /* lane 0 has work lane 1 is not ordered after: 1 up to an
+			      * event yet to record, 2 up to the event of join_epoch */
+	int fork;            /* lane 1 had launches at a join since lane 0's last launch */
+	uint32_t join_epoch; /* dirty == 2: lane 0's epoch closed behind the join */
 } lane_state;
 
 static inline void lane_init(lane_state *s, int lanes)
@@ -186,7 +228,22 @@ static inline int lane_launch(lane_state *s, const lane_access *a, lane_act *act
 	lane_ring *r = &s->r[l], *ro = &s->r[o];
 
 	s->next = o;
-	if (l == 1 && s->dirty) {
+	if (l == 0 && s->fork) {
+		/* the first launch after a join that found lane 1 busy: lane 1 will
+		 * be used again, let it wait for the join and not for this launch */
+		if (s->dirty == 1) {
+			lane_close(s, 0, acts, nacts);
+			s->join_epoch = s->r[0].epoch - 1u;
+			s->dirty = 2;
+		}
+		s->fork = 0;
+	}
+	if (l == 1 && s->dirty == 2) {
+		/* behind the join: that event is there already */
+		lane_act_add(acts, nacts, LANE_WAIT, 0, s->join_epoch);
+		lane_drop(&s->r[0], s->join_epoch);
+		s->dirty = 0;
+	} else if (l == 1 && s->dirty) {
 		/* behind everything on the context stream */
 		lane_close(s, 0, acts, nacts);
 		lane_act_add(acts, nacts, LANE_WAIT, 0, s->r[0].epoch - 1u);
@@ -207,8 +264,18 @@ static inline int lane_launch(lane_state *s, const lane_access *a, lane_act *act
 			r->epoch_of[k++] = r->epoch_of[i];
 		}
 	r->n = k;
-	if (r->n == LANE_RING)
-		lane_wait_epoch(s, l, r->epoch_of[0], acts, nacts);
+	if (r->n == LANE_RING) {
+		if (l == 0 && (s->dirty == 1 || (s->dirty == 2 && r->epoch_of[0] <= s->join_epoch))) {
+			/* lane 1 waits for the oldest before its next launch anyway */
+			for (uint32_t i = 1; i < r->n; i++) {
+				r->a[i - 1u] = r->a[i];
+				r->epoch_of[i - 1u] = r->epoch_of[i];
+			}
+			r->n--;
+		} else {
+			lane_wait_epoch(s, l, r->epoch_of[0], acts, nacts);
+		}
+	}
 	r->a[r->n] = *a;
 	r->epoch_of[r->n] = r->epoch;
 	r->n++;
@@ -217,15 +284,18 @@ static inline int lane_launch(lane_state *s, const lane_access *a, lane_act *act
 }
 
 /* Before any other use of the context stream: lane 0 waits for lane 1's
- * recorded launches. */
+ * recorded launches. The next launch takes lane 0. */
 static inline void lane_join(lane_state *s, lane_act *acts, int *nacts)
 {
 	lane_ring *r = &s->r[1];
 
 	*nacts = 0;
-	if (r->n)
+	if (r->n) {
 		lane_wait_epoch(s, 1, r->epoch_of[r->n - 1u], acts, nacts);
+		s->fork = 1;
+	}
 	s->dirty = 1;
+	s->next = 0;
 }
 
 /* one lane (all launches on lane 0, after a join) or two */

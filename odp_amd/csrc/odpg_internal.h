@@ -449,6 +449,11 @@ void odpg_ctx_unref(struct odpg_ctx_s *ctx);
  * "launch lanes"); unlike the public odpg_ctx_stream() the context keeps
  * its lanes */
 void *odpg_ctx_stream_joined(struct odpg_ctx_s *ctx);
+/* a test entry, not public API: odpg_counters_fold for the rows of one launch
+ * lane only (0 or 1), into the same word layout; -EINVAL for a set of rows
+ * the object does not have */
+struct odpg_counters_s;
+int odpg_counters_fold_lane(struct odpg_counters_s *cnt, int lane, uint64_t *words);
 #ifdef __cplusplus
 }
 #endif

@@ -54,8 +54,9 @@ struct odpg_ctx_s {
 	bool own_stream;
 	hipStream_t copy_stream;
 	/* launch lanes (lanes.h): lane 0 is `stream`, lane 1 `lane1`; verdict-only
-	 * launches alternate between them, every other use of the context stream
-	 * goes through ctx_stream() / ctx_stream_locked(), which join first */
+	 * launches and launches counted into per-lane rows alternate between them,
+	 * every other use of the context stream goes through ctx_stream() /
+	 * ctx_stream_locked(), which join first */
 	hipStream_t lane1;
 	hipEvent_t lane_ev[2][LANE_NEV];
 	lane_state ls;
@@ -97,8 +98,9 @@ struct odpg_counters_s {
 	odpg_ctx_t *ctx;
 	uint64_t qsig;
 	uint32_t ncos, ncols, words, rows;
+	uint32_t sets;                 /* row sets: one per launch lane, or 1 (launches stay serial) */
 	uint32_t any_cos;              /* some CoS has stats_enable */
-	uint64_t *drows;               /* device, rows x words */
+	uint64_t *drows;               /* device, sets x rows x words */
 	uint32_t *dqcol;               /* device, queue column of each CoS */
 	uint64_t *dsum;                /* device, words (fold target) */
 	uint64_t *hsum;                /* pinned host, words */
@@ -197,7 +199,7 @@ static int lane_apply(odpg_ctx_t *c, const lane_act *acts, int n)
 	return 0;
 }
 
-/* The context stream for anything but a verdict-only launch: ordered after
+/* The context stream for anything but a launch on the lanes: ordered after
  * every launch already enqueued on either lane (c->lock held). */
 static hipStream_t ctx_stream_locked(odpg_ctx_t *c)
 {
@@ -683,7 +685,11 @@ int odpg_counters_create(odpg_ctx_t *c, const odpg_table_t *t, odpg_counters_t *
 		counters_free(k);
 		return -E2BIG;
 	}
-	const size_t rb = (size_t)k->rows * k->words * 8u;
+	/* a set of rows per launch lane, so that launches on both lanes never
+	 * share a row; where two sets do not fit the object keeps one and its
+	 * launches stay on the context stream */
+	k->sets = c->lane1 && 2u * ((size_t)k->rows * k->words * 8u) <= CNT_MAX_BYTES ? 2u : 1u;
+	const size_t rb = (size_t)k->sets * k->rows * k->words * 8u;
 
 	if (hipMalloc(&k->drows, rb) != hipSuccess ||
 	    hipMalloc(&k->dqcol, (size_t)(k->ncos + 1u) * 4u) != hipSuccess ||
@@ -728,10 +734,9 @@ void odpg_counters_destroy(odpg_counters_t *k)
 	counters_free(k);
 }
 
-int odpg_counters_fold(odpg_counters_t *k, uint64_t *words)
+/* sum and clear row sets [set0, set0 + nsets) into `words` */
+static int counters_fold_sets(odpg_counters_t *k, uint32_t set0, uint32_t nsets, uint64_t *words)
 {
-	if (!k || !words)
-		return -EINVAL;
 	odpg_ctx_t *c = k->ctx;
 	std::lock_guard<std::mutex> fl(k->lock);
 
@@ -741,7 +746,8 @@ int odpg_counters_fold(odpg_counters_t *k, uint64_t *words)
 		std::lock_guard<std::mutex> g(c->lock);
 		hipStream_t cs = ctx_stream_locked(c);
 
-		if (odpg_launch_counters_fold(k->drows, k->rows, k->words, k->dsum, cs) ||
+		if (odpg_launch_counters_fold(k->drows + (size_t)set0 * k->rows * k->words,
+					      nsets * k->rows, k->words, k->dsum, cs) ||
 		    hipMemcpyAsync(k->hsum, k->dsum, (size_t)k->words * 8u, hipMemcpyDeviceToHost,
 				   cs) != hipSuccess ||
 		    hipMemsetAsync(k->dsum, 0, (size_t)k->words * 8u, cs) != hipSuccess ||
@@ -758,6 +764,21 @@ int odpg_counters_fold(odpg_counters_t *k, uint64_t *words)
 		for (uint32_t q = 0; q < k->nq[i]; q++)
 			uq[(size_t)i * ODPG_COS_QUEUE_MAX + q] += dl[k->qcol[i] + q];
 	return 0;
+}
+
+int odpg_counters_fold(odpg_counters_t *k, uint64_t *words)
+{
+	if (!k || !words)
+		return -EINVAL;
+	return counters_fold_sets(k, 0, k->sets, words);
+}
+
+/* odpg_internal.h: the rows launches on `lane` added into, for the tests */
+int odpg_counters_fold_lane(odpg_counters_t *k, int lane, uint64_t *words)
+{
+	if (!k || !words || lane < 0 || (uint32_t)lane >= k->sets)
+		return -EINVAL;
+	return counters_fold_sets(k, (uint32_t)lane, 1, words);
 }
 
 /* ---- delivery lists (odpg_deliver.h; kernels in deliver.hip) ------------- */
@@ -1527,9 +1548,11 @@ static int validate_batch(const odpg_batch_t *b)
 	return 0;
 }
 
-static int classify_on(odpg_ctx_t *c, hipStream_t s, const odpg_table_t *t,
+/* one launch on lane `lane` (0: the context stream) */
+static int classify_on(odpg_ctx_t *c, int lane, const odpg_table_t *t,
 		       const odpg_batch_t *b, const odpg_result_t *r, void *ws)
 {
+	hipStream_t s = lane ? c->lane1 : c->stream;
 	odpg_launch_args a;
 	const dtable_hdr_t &h = t->hdr;
 	uint32_t grid = odpg_launch_grid(b->num);
@@ -1620,7 +1643,8 @@ static int classify_on(odpg_ctx_t *c, hipStream_t s, const odpg_table_t *t,
 	if (r->counters) {
 		odpg_counters_t *k = r->counters;
 
-		a.cnt.row = k->drows;
+		/* the lane's own rows: launches of a lane are stream-ordered */
+		a.cnt.row = k->drows + (size_t)lane * k->rows * k->words;
 		a.cnt.qcol = k->dqcol;
 		a.cnt.words = k->words;
 		a.cnt.rows = k->rows;
@@ -1753,14 +1777,17 @@ int odpg_classify(odpg_ctx_t *c, const odpg_table_t *t, const odpg_batch_t *b,
 	hipSetDevice(c->device);
 	if ((rc = ensure_ws(c, ws_need(t, b->num, r->stats != nullptr))))
 		return rc;
-	if (r->stats || r->counters || c->ls.lanes != 2)
-		/* counted launches add into workgroup-owned rows with plain
-		 * read-modify-writes and stats launches share the context's
-		 * scratch: both stay in order on the context stream */
-		return classify_on(c, ctx_stream_locked(c), t, b, r, c->ws);
-	/* verdict-only: the next lane, behind whatever on the other lane touches
-	 * the same bytes (lanes.h). Descriptor batches bound their frame bytes by
-	 * the descriptor format (32-bit offset + 32-bit length) */
+	if (r->stats || (r->counters && r->counters->sets != 2) || c->ls.lanes != 2) {
+		/* stats launches share the context's scratch, and counted launches
+		 * add into workgroup-owned rows with plain read-modify-writes: with
+		 * one set of rows they stay in order on the context stream */
+		ctx_stream_locked(c);
+		return classify_on(c, 0, t, b, r, c->ws);
+	}
+	/* verdict-only, or counted into the lane's own set of rows: the next lane,
+	 * behind whatever on the other lane touches the same bytes (lanes.h).
+	 * Descriptor batches bound their frame bytes by the descriptor format
+	 * (32-bit offset + 32-bit length) */
 	const uintptr_t f = (uintptr_t)b->frames, o = (uintptr_t)r->out;
 	lane_access acc = {};
 	lane_act acts[LANE_MAX_ACTS];
@@ -1778,7 +1805,7 @@ int odpg_classify(odpg_ctx_t *c, const odpg_table_t *t, const odpg_batch_t *b,
 
 	if (lane_apply(c, acts, n))
 		return -EIO;
-	return classify_on(c, lane ? c->lane1 : c->stream, t, b, r, c->ws);
+	return classify_on(c, lane, t, b, r, c->ws);
 }
 
 /* Host-buffer path: frames/desc/results in host memory (pinned is fastest).
@@ -1895,7 +1922,7 @@ int odpg_classify_host(odpg_ctx_t *c, const odpg_table_t *t, const odpg_batch_t 
 		cr.meta = r->meta ? B.meta : nullptr;
 		cr.stats = r->stats ? c->stage_stats : nullptr;
 		cr.counters = r->counters;
-		if (classify_on(c, cs, t, &cb, &cr, c->ws)) {
+		if (classify_on(c, 0, t, &cb, &cr, c->ws)) {
 			err = -EIO;
 			break;
 		}
